@@ -7,7 +7,21 @@ memLevel=4, windowBits=15 and Beast's pmd framing (impl_base.hpp:85-154),
 resident in HBM.  One step = one batched inflate launch over the whole
 batch; `value` is that inflate rate.
 
-Also reported (same JSON line, key "deflate"): configs[2] ("C3"), the
+A plain run (`--gpus N --steps K --warmup W`) does only that: it builds the
+C2 inputs, warms up, times the K steps, writes the last step's outputs when
+`--dump-outputs DIR` is given, and prints the result line (the contract's
+keys, the config, and the roofline from the timed steps' own HIP events).
+Everything below runs only with `--full`.
+
+`--dump-outputs DIR` writes what the last timed step returned, as .npy files:
+`status` and `out_len` (float32, one entry per message), `out_msg_sum`
+(float64, the byte sum of every inflated message), and `out_sample` (float32,
+the bytes of a fixed seeded sample of messages, whose indices are in
+`out_sample_index`).  The inputs are seeded, so two builds given the same
+arguments can be compared output for output.
+
+With `--full` the line also reports the parity check of the C2 output
+against the plaintext and, under key "deflate", configs[2] ("C3"): the
 round trip of 64 Ki x 4 KiB JSON (seed 0x5EED0003) through the GPU deflater
 and back through the GPU inflater -- deflate GiB/s, round-trip GiB/s,
 compressed size vs Beast's deflate at the same level.  Key "mixed":
@@ -22,7 +36,7 @@ may use, by the C restatement of Beast's zlib ("port") and by the
 reference's own zlib 1.3.1 compiled from its sources (oracle/_ref, when
 present).
 
-Launch:  python bench.py [--gpus N --steps K --warmup W]
+Launch:  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
 N > 1 runs under torch.distributed.run (started here as a child process when
 no launcher set WORLD_SIZE; under one, WORLD_SIZE must equal N): every rank works on its own 64 Ki
 messages (independent streams under no_context_takeover), so there is no
@@ -520,15 +534,49 @@ def mixed_legs(args, rank, world, timer, dev):
     return out
 
 
+LINE_KEYS = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+             "vs_baseline", "dtype", "data", "config", "parity_ok")
+
+DUMP_SAMPLE_MSGS = 2048      # --dump-outputs: messages whose bytes are written whole (32 MiB as float32)
+DUMP_SAMPLE_SEED = 0x5EED00D0
+
+
+def plain_line(result):
+    """The stdout line of a plain run: the contract's keys, the config and the
+    C2 roofline from the timed steps' own HIP events."""
+    line = {k: result[k] for k in LINE_KEYS if k in result and k != "parity_ok"}   # no parity check ran
+    line["roofline"] = result["roofline"]
+    return line
+
+
+def dump_outputs(dirname, res, out, n, rank, world):
+    """--dump-outputs: what the last timed inflate step returned (`res`, whose
+    bytes are in `out`, one MSG_BYTES slot per message), as DIR/<name>.npy in
+    float32 / float64: status and length of every message, the byte sum of
+    every message, and the bytes of a fixed seeded sample of messages."""
+    os.makedirs(dirname, exist_ok=True)
+    torch.cuda.synchronize()
+    msgs = out[: n * MSG_BYTES].view(n, MSG_BYTES)
+    sums = torch.cat([msgs[a:a + 4096].sum(dim=1, dtype=torch.int64) for a in range(0, n, 4096)])
+    idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=min(n, DUMP_SAMPLE_MSGS), replace=False))
+    sample = msgs[torch.from_numpy(idx).to(out.device)]
+    arrays = {"status": res.status.cpu().numpy().astype(np.float32),
+              "out_len": res.out.len.cpu().numpy().astype(np.float32),
+              "out_msg_sum": sums.cpu().numpy().astype(np.float64),
+              "out_sample_index": idx.astype(np.float64),
+              "out_sample": sample.cpu().numpy().astype(np.float32)}
+    suffix = f"_rank{rank}" if world > 1 else ""
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, f"{name}{suffix}.npy"), a)
+
+
 def compact_line(full):
     """The bench's stdout line: the contract's keys, the C2 roofline and CPU
     baseline, and every north-star number (C3 deflate and size, C4 / C5
     deflate, inflate of this library's and of a Beast peer's payloads, the
     projected 2 / 4 / 8-way speed-ups, the legs' CPU columns, parity).  The
     whole record goes to gpurun_out/bench_detail.json."""
-    keys = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
-            "vs_baseline", "dtype", "data", "config", "parity_ok")
-    line = {k: full[k] for k in keys if k in full}
+    line = {k: full[k] for k in LINE_KEYS if k in full}
     rf = dict(full["roofline"])
     src = rf.pop("traffic_source", None)
     rf["traffic_source"] = src.get("source") if isinstance(src, dict) else src
@@ -619,6 +667,11 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--msgs", type=int, default=N_MSGS)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (see the module docstring)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything besides the headline: the C2 parity check, the frame passes, C3, the "
+                         "C4 / C5 legs, the CPU baselines and the PMC traffic lookup (the --no-* options trim it)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-exact", action="store_true", help="skip the exact-mode (BPMD_F_EXACT) deflate leg")
     ap.add_argument("--no-deflate", action="store_true")
@@ -632,6 +685,8 @@ def main():
     ap.add_argument("--c4-msgs", type=int, default=C4_MSGS, help="configs[3] batch (all ranks together)")
     ap.add_argument("--c5-msgs", type=int, default=C5_MSGS, help="configs[4] batch (all ranks together)")
     args = ap.parse_args()
+    if not args.full:   # a plain run: the headline only
+        args.no_cpu_baseline = args.no_deflate = args.no_frame = args.no_mixed = True
     rc = maybe_launch(args, sys.argv[1:])
     if rc is not None:
         sys.exit(rc)
@@ -671,16 +726,24 @@ def main():
     out_off = pmd.slot_offsets(cap)
     out = torch.empty(n * MSG_BYTES + 64, dtype=torch.uint8, device=dev)
 
+    last = [None]   # what the newest step returned (--dump-outputs writes the last timed step's)
+
     def inflate_step():
-        return pmd.inflate_batch(src, cap, out=out, out_off=out_off)
+        last[0] = pmd.inflate_batch(src, cap, out=out, out_off=out_off)
+        return last[0]
 
     r = inflate_step()
     torch.cuda.synchronize()
-    ok = int((r.status != 0).sum()) == 0 and torch.equal(
-        out[: n * MSG_BYTES].view(n, MSG_BYTES), torch.from_numpy(raw.reshape(n, MSG_BYTES)).to(dev))
-    if not ok:
-        log(f"[rank {rank}] C2 PARITY FAILURE")
+    ok = None
+    if args.full:
+        ok = int((r.status != 0).sum()) == 0 and torch.equal(
+            out[: n * MSG_BYTES].view(n, MSG_BYTES), torch.from_numpy(raw.reshape(n, MSG_BYTES)).to(dev))
+        if not ok:
+            log(f"[rank {rank}] C2 PARITY FAILURE")
     step_s, kern_ms = timer.run(inflate_step, args.steps, args.warmup)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last[0], out, n, rank, world)
+    last[0] = None
 
     uncomp = n * MSG_BYTES
     comp = int(comp_len.astype(np.int64).sum())
@@ -688,7 +751,7 @@ def main():
     alg_bytes = comp + uncomp + 16 * n
     achieved = alg_bytes / (kern_ms * 1e-3) / 1e9
     kname = "inflate_lane3_kernel" if n >= 2048 else "inflate_kernel"   # bpmd_set_inflate_kernel(0) policy
-    traffic, traffic_src = pmc_traffic(kname) if n == N_MSGS else (None, None)
+    traffic, traffic_src = pmc_traffic(kname) if args.full and n == N_MSGS else (None, None)
     # (traffic_src: the PMC file, its raw FETCH/WRITE bytes and the FETCH calibration used)
     result = {
         "metric": "GiB/s device-resident inflate+deflate over batched WS payloads, 1/2/4/8 GPU",
@@ -706,7 +769,7 @@ def main():
         "config": {"workload": "C2 inflate-only: 64Ki x 4KiB payloads/GPU, compLevel=6, memLevel=4, windowBits=15",
                    "msgs_per_gpu": n, "msg_bytes": MSG_BYTES, "compressed_bytes_per_gpu": comp,
                    "parallelism": f"dp{world} (independent message shards)"},
-        "parity_ok": bool(ok),
+        "parity_ok": None if ok is None else bool(ok),
         "roofline": {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic,
                      "traffic_source": traffic_src,
@@ -889,7 +952,9 @@ def main():
                          f"t_port_over_t_zlib_{T}threads": icpu.get(f"t_port_over_t_zlib_{T}threads")},
                 "system_zlib": (icpu.get("system") or {}).get(f"{T}_threads"),
                 "cpu_model": cpu["cpu_model"], "nproc": cpu["nproc"], "cores_available": cpu["cores_available"]}
-    if rank == 0:
+    if rank == 0 and not args.full:
+        print(json.dumps(plain_line(result)), flush=True)
+    elif rank == 0:
         # the whole record to a side file; stdout gets one line under ~4 KB
         # with every north-star number (the driver keeps only a tail of it)
         try:

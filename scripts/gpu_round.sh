@@ -48,12 +48,12 @@ for s in "$@"; do
       grep "C1 echo" gpurun_out/${TAG}_c1_echo.log ;;
     bench)
       step bench
-      bash scripts/run_bench.sh ${TAG}_bench 900 "d['value'], d['parity_ok']" || exit 14
+      bash scripts/run_bench.sh ${TAG}_bench 900 "d['value'], d['parity_ok']" --full || exit 14
       wc -c gpurun_out/${TAG}_bench.json ;;
     c2)
       step c2
       bash scripts/run_bench.sh ${TAG}_c2 300 "d['value'], d['roofline']['kernel_ms'], d['parity_ok']" \
-        --steps 10 --warmup 2 --no-cpu-baseline --no-mixed --no-deflate --no-frame --no-exact || exit 15 ;;
+        --steps 10 --warmup 2 --full --no-cpu-baseline --no-mixed --no-deflate --no-frame --no-exact || exit 15 ;;
     ab)
       step "ab ${VARIANTS}"
       for r in $(seq ${ROUNDS:-3}); do
@@ -61,7 +61,7 @@ for s in "$@"; do
           if [ "$v" = default ]; then L=beast_amd/libbeast_pmd.so; else L=beast_amd/libbeast_pmd_$v.so; fi
           BPMD_LIB=$L bash scripts/run_bench.sh ${TAG}_ab_${v}_$r 300 \
             "'$v', d['value'], d['roofline']['kernel_ms'], d['parity_ok'], d.get('north_star',{}).get('c3',{}).get('deflate')" \
-            --steps 10 --warmup 2 --no-cpu-baseline --no-mixed --no-frame --no-exact ${AB_ARGS} || exit 16
+            --steps 10 --warmup 2 --full --no-cpu-baseline --no-mixed --no-frame --no-exact ${AB_ARGS} || exit 16
         done
       done ;;
     prof)

@@ -36,6 +36,20 @@ def test_single_gpu_runs_in_process(monkeypatch):
     assert bench.maybe_launch(types.SimpleNamespace(gpus=1), []) is None
 
 
+def test_plain_line_is_the_headline_only():
+    """A plain run's line: the contract's keys as the full line has them, the
+    roofline, no parity verdict (no check ran) and nothing of the other legs."""
+    result = {"metric": "m", "value": 1.5, "unit": "GiB/s", "n_gpus": 1, "steps": 4, "warmup": 2, "ms_per_step": 0.25,
+              "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8", "data": "d",
+              "config": {"msgs_per_gpu": 8}, "parity_ok": None, "roofline": {"frac": 0.1, "traffic_source": None},
+              "deflate": {"deflate_value": 1.0}}
+    line = bench.plain_line(result)
+    assert set(line) == set(bench.LINE_KEYS) - {"parity_ok"} | {"roofline"}
+    assert all(line[k] == result[k] for k in line)
+    full = bench.compact_line(dict(result, parity_ok=True, deflate=None))
+    assert all(full[k] == line[k] for k in line if k != "roofline")
+
+
 PROBE = r"""
 import json, os, sys
 import torch.distributed as dist

@@ -19,7 +19,7 @@ def test_bench_gpus_2_launches_two_ranks():
     env = dict(os.environ, BPMD_BENCH_BACKEND="gloo")
     env.pop("WORLD_SIZE", None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--msgs", "4096", "--no-mixed", "--no-cpu-baseline", "--no-deflate", "--no-frame"]
+           "--msgs", "4096", "--full", "--no-mixed", "--no-cpu-baseline", "--no-deflate", "--no-frame"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=110, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [json.loads(x) for x in r.stdout.splitlines() if x.startswith("{")]
