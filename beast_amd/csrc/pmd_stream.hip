@@ -696,6 +696,8 @@ void inflate_batch(Arena& A, std::vector<Job*>& jobs)
     using bpmd::zst::ZCall;
     const uint32_t k = (uint32_t)jobs.size();
     std::vector<size_t> ioff(k), ooff(k);
+    // packed on the kernel's contract (tests/test_gpu_zstream_guard.py): no store at or past out + cap, and
+    // results that do not depend on the 64 bytes after in + n_in (stale bytes of earlier batches here)
     size_t o = up256(sizeof(ZCall) * k);
     for (uint32_t i = 0; i < k; ++i) {
         ioff[i] = o;

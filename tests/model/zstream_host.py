@@ -149,13 +149,24 @@ class HostInflater:
     def reset(self, wbits=15):
         self.L.zs_host_reset(self.st, wbits)
 
+    SLACK = 64            # bytes after the input that the staging loads may read
+    poison = 0x00         # ... and what they hold
+    canary = None         # GuardedHostInflater: the byte after the output room
+
     def write(self, zs, flush):
         n = zs.avail_in
         cap = min(zs.avail_out, 1040 * n + 8192)
-        src = ctypes.create_string_buffer(ctypes.string_at(zs.next_in, n) if n else b"", n + 64)
-        dst = ctypes.create_string_buffer(cap + 64)
+        src = ctypes.create_string_buffer((ctypes.string_at(zs.next_in, n) if n else b"") +
+                                          bytes([self.poison]) * self.SLACK, n + self.SLACK)
+        fill = bytes([0 if self.canary is None else self.canary])
+        dst = ctypes.create_string_buffer(fill * (cap + 64), cap + 64)
         res = Result()
         self.L.zs_host_write(self.st, src, n, dst, cap, flush, ctypes.byref(res))
+        if self.canary is not None:
+            self.calls += 1
+            assert res.out_used <= cap, (res.out_used, cap)
+            assert dst.raw[cap:] == fill * 64, ("store past out + cap", n, cap, flush)
+            assert src.raw[n:] == bytes([self.poison]) * self.SLACK
         if res.out_used:
             ctypes.memmove(zs.next_out, dst, res.out_used)
         if res.published:
@@ -167,3 +178,20 @@ class HostInflater:
             zs.total_out += res.out_used
             zs.data_type = res.data_type
         return res.ec
+
+
+class GuardedHostInflater(HostInflater):
+    """HostInflater with the call's buffers watched: 64 canary bytes after
+    out + cap that no call may change, and the 64 bytes after in + n_in (the
+    staging loads read up to 15 of them) filled with `poison`, on which no
+    result may depend."""
+    canary = 0xA5
+    total_calls = 0
+
+    def __init__(self, wbits=15, poison=0x5A):
+        super().__init__(wbits)
+        self.poison = poison
+        self.calls = 0
+
+    def close(self):
+        GuardedHostInflater.total_calls += self.calls

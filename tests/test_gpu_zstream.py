@@ -12,14 +12,22 @@ caller's buffer (tests/zstream_cases.py):
 * input a byte at a time, output a byte at a time, every Flush value, the
   Flush::trees known answers, the reference's inflate KATs split at every
   byte, stored blocks, small windows (the per-call window rule,
-  inflate_stream.ipp:1046-1061), end of stream, corrupted input and BAD mode;
+  inflate_stream.ipp:1046-1061), end of stream and corrupted input (bit
+  flips the oracle fails on), each also with every call of the list made
+  after the end or the failure (drive(stop=False)): a connection that keeps
+  calling an inflater in DONE or BAD mode;
 * websocket::stream's read path replayed on both sides (read.hpp:1284-1385:
   rd_buf advanced by total_in, inflate_with_eb with rd_eb_consumed): the
   reference's issue 3028 (three context-takeover messages read one byte per
   read_some, read3.cpp:1133-1226) and issue 1630 (four packets whose
   deflate blocks split UTF-8 characters, read3.cpp:619-1009);
 * configs[0]'s shape (1 Ki x 1 KiB messages on one connection) with the
-  stream's memory bounded."""
+  stream's memory bounded.
+
+Every call here is a launch of its own.  The same checks on calls that share
+a launch (the micro-batcher) are tests/test_gpu_stream_batch.py; that no call
+stores past its room or depends on the bytes after its input is
+tests/test_gpu_zstream_guard.py."""
 import ctypes
 
 import pytest
@@ -103,6 +111,8 @@ def test_small_window_call_split_rule():
 
 
 def test_end_of_stream_then_done_mode():
+    """... and twelve more calls to the finished inflater (rooms of 65536, 1
+    and 0, four flushes, trailing bytes offered): end_of_stream every time."""
     Z.case_end_of_stream(make)
 
 
@@ -111,6 +121,8 @@ def test_stored_blocks():
 
 
 def test_errors_then_bad_mode():
+    """Bit-flipped streams (eight of them chosen so that the oracle fails),
+    and the calls made to the failed inflater afterwards."""
     Z.case_errors(make)
 
 

@@ -68,7 +68,36 @@ def test_stored_blocks():
 
 
 def test_errors():
+    """(with the calls a connection makes after the error: BAD mode)"""
     Z.case_errors(make)
+
+
+@pytest.mark.parametrize("poison", [0x00, 0x5A, 0xFF])
+def test_calls_stay_inside_their_buffers(poison):
+    """The kernel contract the batcher's packing relies on (pmd_stream.hip
+    inflate_batch; the 64-lane build: tests/test_gpu_zstream_guard.py): no
+    store at or past out + cap (64 canary bytes there stay as they were) and
+    results that do not depend on the bytes after in + n_in, which the
+    16-byte staging loads read (the oracle's records whatever they hold)."""
+    def guarded(wbits):
+        return H.GuardedHostInflater(wbits, poison)
+
+    before = H.GuardedHostInflater.total_calls
+    Z.case_connection_random_cuts(guarded, "json", 6, 4)
+    Z.case_connection_random_cuts(guarded, "random", 1, 4)
+    Z.case_flush_mix(guarded)
+    Z.case_stored_blocks(guarded)
+    Z.case_errors(guarded)
+    Z.case_small_window(guarded)
+    assert H.GuardedHostInflater.total_calls - before > 1000   # the guards were in place
+
+
+def test_lockstep_plans_every_call():
+    """The plans of the GPU lockstep and guard tests (Z.mixed_plans), every
+    call made whatever the status, guarded, against the oracle."""
+    for R, seed in ((100, 0), (40, 0), (40, 1)):
+        for name, (stream, wbits, calls) in Z.mixed_plans(R, seed):
+            Z.compare(lambda w: H.GuardedHostInflater(w, 0xFF), stream, calls, wbits=wbits, label=name, stop=False)
 
 
 def test_issue3028_one_byte_reads():

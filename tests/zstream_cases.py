@@ -6,7 +6,10 @@ status, next_in / avail_in / total_in, next_out / avail_out / total_out,
 data_type, and the bytes in the caller's buffer (also after an error, which
 returns without advancing z_params, inflate_stream.ipp:120-125).
 
-Used by tests/test_gpu_zstream.py (the kernel, through the C ABI) and
+Used by tests/test_gpu_zstream.py (the kernel, through the C ABI, a launch
+per call), tests/test_gpu_stream_batch.py (calls sharing a launch: plans of a
+fixed call count run in lockstep, run_lockstep), tests/test_gpu_zstream_guard.py
+(the kernels launched directly, inside guarded rooms) and
 tests/test_zstream_host.py (the kernel's own source built for the host)."""
 import ctypes
 import json
@@ -37,12 +40,14 @@ class OracleInflater:
         return self.z.write(zs, FLUSH_NAMES[flush])
 
 
-def drive(inf, stream: bytes, calls):
+def drive(inf, stream: bytes, calls, stop=True, before=None):
     """calls: [(cut, avail_out, flush)].  Each call offers input from where
     the inflater's next_in stands to max(cut, that).  Returns one record per
     call: (status, total_in, avail_in, total_out, avail_out, data_type,
-    in position, out position, the whole output buffer); stops after an
-    error or end_of_stream."""
+    in position, out position, the whole output buffer).  stop=True ends
+    after the first error or end_of_stream; stop=False makes every call in the
+    list whatever the status (a connection that keeps calling an inflater in
+    BAD or DONE mode).  before(), if given, runs ahead of every write()."""
     src = ctypes.create_string_buffer(stream, max(1, len(stream)))
     base = ctypes.addressof(src)
     pos = 0
@@ -51,6 +56,8 @@ def drive(inf, stream: bytes, calls):
         cut = max(cut, pos)
         buf = ctypes.create_string_buffer(max(1, room))
         zs = ZParams(base + pos if cut > pos else None, cut - pos, 0, ctypes.addressof(buf), room, 0, 12345)
+        if before:
+            before()
         st = inf.write(zs, flush)
         assert st >= 0, f"C ABI error {st}"
         in_at = (zs.next_in - base) if zs.next_in else pos
@@ -58,7 +65,7 @@ def drive(inf, stream: bytes, calls):
         recs.append((st, zs.total_in, zs.avail_in, zs.total_out, zs.avail_out, zs.data_type, in_at, out_at,
                      buf.raw))
         pos += zs.total_in
-        if st >= 2:
+        if stop and st >= 2:
             break
     return recs
 
@@ -66,23 +73,41 @@ def drive(inf, stream: bytes, calls):
 FIELDS = ("status", "total_in", "avail_in", "total_out", "avail_out", "data_type", "next_in", "next_out", "bytes")
 
 
-def compare(make, stream, calls, wbits=15, label=""):
-    """make(wbits) -> inflater under test.  Asserts every call equal to the
-    oracle's; returns the oracle's records."""
-    want = drive(OracleInflater(wbits), stream, calls)
-    inf = make(wbits)
-    try:
-        got = drive(inf, stream, calls)
-    finally:
-        close = getattr(inf, "close", None)
-        if close:
-            close()
+def assert_records_equal(got, want, calls, label=""):
+    """Every call of `got` equal to the oracle's `want` over all of FIELDS."""
     for i in range(min(len(got), len(want))):
         for f, a, b in zip(FIELDS, got[i], want[i]):
             assert a == b, (label, "call", i, f, a if f != "bytes" else len(a), b if f != "bytes" else len(b),
                             calls[i], O.ERRORS[got[i][0]], O.ERRORS[want[i][0]])
     assert len(got) == len(want), (label, len(got), len(want))
+
+
+def compare(make, stream, calls, wbits=15, label="", stop=True):
+    """make(wbits) -> inflater under test.  Asserts every call equal to the
+    oracle's; returns the oracle's records.  stop: see drive()."""
+    want = drive(OracleInflater(wbits), stream, calls, stop=stop)
+    inf = make(wbits)
+    try:
+        got = drive(inf, stream, calls, stop=stop)
+    finally:
+        close = getattr(inf, "close", None)
+        if close:
+            close()
+    assert_records_equal(got, want, calls, label)
     return want
+
+
+def calls_after(recs, pred):
+    """How many of the records follow the first one whose status satisfies
+    pred (the calls a connection made to an inflater already in that state)."""
+    for i, r in enumerate(recs):
+        if pred(r[0]):
+            return len(recs) - i - 1
+    return 0
+
+
+def is_error(st):
+    return st > 2   # zlib::error: 1 need_buffers and 2 end_of_stream are not failures
 
 
 def connection_stream(msgs, level=6, wbits=15, mem=4, takeover=True):
@@ -324,10 +349,17 @@ def case_end_of_stream(make):
     import zlib
     c = zlib.compressobj(6, zlib.DEFLATED, -15, 8)
     stream = c.compress(b"hello world " * 300) + c.flush(zlib.Z_FINISH) + b"trailing garbage"
+    eos = O.ERROR_CODES["end_of_stream"]
     for cuts in ([len(stream)], [10, 40, len(stream)], list(range(1, len(stream) + 1, 3))):
         calls = [(x, 1 << 16, SYNC) for x in cuts] + [(len(stream), 1 << 16, SYNC)] * 3
         want = compare(make, stream, calls, label=f"eos {len(cuts)}")
-        assert want[-1][0] == O.ERROR_CODES["end_of_stream"]
+        assert want[-1][0] == eos
+        # the connection keeps calling: DONE mode answers end_of_stream again,
+        # with the trailing bytes offered and with every flush
+        more = calls + [(len(stream), room, fl) for room in (1 << 16, 1, 0) for fl in (SYNC, FINISH, BLOCK, TREES)]
+        want = compare(make, stream, more, label=f"eos {len(cuts)} then DONE", stop=False)
+        assert len(want) == len(more) and calls_after(want, lambda st: st == eos) >= 12
+        assert all(r[0] == eos for r in want[-12:])
 
 
 def case_stored_blocks(make):
@@ -344,13 +376,43 @@ def case_errors(make):
     rng = random.Random(3)
     msgs = msgs_of("json", [4096] * 4, seed=4)
     good = bytearray(connection_stream(msgs, level=6, mem=4))
+    after = 0
     for trial in range(12):
         bad = bytearray(good)
         at = rng.randrange(len(bad) // 3, len(bad))
         bad[at] ^= 1 << rng.randrange(8)
         calls = random_calls(rng, len(bad), rng.choice([1, 5, 30]), [4096, 1 << 16, 100])
-        calls += [(len(bad), 1 << 16, SYNC)] * 2   # BAD mode answers need_buffers
+        calls += [(len(bad), 1 << 16, SYNC)] * 2
         compare(make, bytes(bad), calls, label=f"corrupt {trial}@{at}")
+        # the connection keeps calling the dead inflater: every call of the
+        # list is made, BAD mode's answers included
+        want = compare(make, bytes(bad), calls, label=f"corrupt {trial}@{at} then BAD", stop=False)
+        assert len(want) == len(calls)
+        after += calls_after(want, is_error)
+    # most single-bit flips of this stream still decode (the oracle reports no
+    # error for any of the twelve above): flips the oracle does fail on
+    for trial, bad in enumerate(failing_flips(good, rng, 8)):
+        calls = random_calls(rng, len(bad), rng.choice([1, 5, 30]), [4096, 1 << 16, 100])
+        compare(make, bad, calls, label=f"failing {trial}")
+        want = compare(make, bad, calls, label=f"failing {trial} then BAD", stop=False)
+        assert len(want) == len(calls) and calls_after(want, is_error) >= 1, trial
+        after += calls_after(want, is_error)
+    assert after >= 8   # calls made after an error were compared
+
+
+def failing_flips(good, rng, count, before=None):
+    """`count` copies of the stream with one bit flipped (in its last two
+    thirds, or before byte `before`) each of which the oracle's inflater fails
+    on: drawn from rng until it does."""
+    out = []
+    while len(out) < count:
+        bad = bytearray(good)
+        at = rng.randrange(0, before) if before else rng.randrange(len(bad) // 3, len(bad))
+        bad[at] ^= 1 << rng.randrange(8)
+        recs = drive(OracleInflater(15), bytes(bad), [(len(bad), 1 << 20, SYNC)] * 2)
+        if is_error(recs[-1][0]):
+            out.append(bytes(bad))
+    return out
 
 
 def issue3028_message() -> bytes:
@@ -379,3 +441,172 @@ def issue1630_frames():
             out.append((b0 & 0x0f, p[i:i + n]))
             i += n
     return out
+
+
+# ------------------------------------------------ plans of a fixed call count
+# A plan is (stream bytes, windowBits, R calls): what one connection does in R
+# rounds of a lockstep run (run_lockstep) or of a direct kernel launch
+# (tests/test_gpu_zstream_guard.py).
+
+ROOMS = [4096, 65536, 300, 7, 1, 258, 257, 255, 256]
+ALL_FLUSHES = (NONE, BLOCK, PARTIAL, SYNC, FULL, FINISH, TREES)
+
+
+def fixed_calls(stream, calls, R):
+    """The call list cut to exactly R calls: truncated, or padded with drain
+    calls that offer the whole stream."""
+    calls = list(calls[:R])
+    return calls + [(len(stream), 65536, SYNC)] * (R - len(calls))
+
+
+def offering_calls(stream, wbits, R, offers, rooms, flush=SYNC):
+    """R calls that offer exactly offers[i % len] new bytes with a room of
+    rooms[i % len] each.  How far a call gets decides where the next one
+    starts, so the cuts are taken from the oracle's inflater."""
+    inf = OracleInflater(wbits)
+    src = ctypes.create_string_buffer(stream, max(1, len(stream)))
+    pos, calls = 0, []
+    for i in range(R):
+        n = min(offers[i % len(offers)], len(stream) - pos)
+        room = rooms[i % len(rooms)]
+        buf = ctypes.create_string_buffer(max(1, room))
+        zs = ZParams(ctypes.addressof(src) + pos if n else None, n, 0, ctypes.addressof(buf), room, 0, 0)
+        inf.write(zs, flush)
+        calls.append((pos + n, room, flush))
+        pos += zs.total_in
+    return calls
+
+
+_ORACLE = {}
+
+
+def oracle_records(plan):
+    """The oracle's records of every call of the plan (stop=False), computed
+    once per plan and shared; nothing may change them."""
+    stream, wbits, calls = plan
+    key = (stream, wbits, tuple(calls))
+    if key not in _ORACLE:
+        _ORACLE[key] = drive(OracleInflater(wbits), stream, calls, stop=False)
+    return _ORACLE[key]
+
+
+_PLANS = {}
+
+
+def mixed_plans(R, seed=0, rooms=ROOMS):
+    """16 named plans of R calls each whose inflaters are, in any one round,
+    in different phases: block headers, stored copies, the fast loop, pending
+    matches and literals (rooms of 1 and 7), BAD and DONE.  [(name, plan)]."""
+    key = (R, seed, tuple(rooms))
+    if key in _PLANS:
+        return _PLANS[key]
+    import zlib
+    from tests.foreign import foreign_payloads
+    rng = random.Random(f"mixed {seed}")
+    plans = []
+
+    def add(name, stream, calls, wbits=15):
+        plans.append((name, (bytes(stream), wbits, fixed_calls(stream, calls, R))))
+
+    def cuts(stream, rooms_=rooms, flushes=(SYNC,)):
+        return random_calls(rng, len(stream), max(1, R - 8), rooms_, flushes)
+
+    sizes = [0, 1, 100, 1024, 4096, 9000]
+    s = connection_stream(msgs_of("json", [rng.choice(sizes) for _ in range(12)], seed=61 + seed), level=6, mem=4)
+    add("json L6 m4 takeover", s, cuts(s))
+    s = connection_stream(msgs_of("binary", [rng.choice(sizes) for _ in range(12)], seed=62 + seed), level=1, mem=4)
+    add("binary L1", s, cuts(s))
+    s = connection_stream(msgs_of("random", [70000, 5, 3000], seed=63 + seed), level=0, mem=4)
+    add("stored blocks", s, cuts(s, [1 << 17, 4000, 1, 70000] + list(rooms), (SYNC, TREES, BLOCK)))
+    s = connection_stream(msgs_of("corpus1", [9000, 4096, 20000], seed=64 + seed), level=9, mem=9)
+    add("corpus1 L9 m9", s, cuts(s))
+    pays, _, _ = foreign_payloads(21 + seed, 12)
+    s = b"".join(p + EB for p in pays)
+    add("foreign encoders", s, cuts(s))
+    w15 = connection_stream(msgs_of("corpus1", [6000, 6000], seed=9), level=9, wbits=15, mem=8)
+    add("w15 stream at windowBits 9", w15, cuts(w15, [1 << 16, 2000, 64] + list(rooms)), wbits=9)
+    add("w15 stream at windowBits 12", w15, cuts(w15, [1 << 16, 2000, 64] + list(rooms)), wbits=12)
+    # bit flips the oracle fails on, in the first part of the stream so that
+    # BAD mode comes part-way through the R calls and the calls go on
+    good = connection_stream(msgs_of("json", [4096] * 4, seed=4), level=6, mem=4)
+    for k, bad in enumerate(failing_flips(good, rng, 2, before=len(good) // 2)):
+        add(f"bit flip {k}", bad, cuts(bad, [4096, 1 << 16, 100]))
+    c = zlib.compressobj(6, zlib.DEFLATED, -15, 8)
+    s = c.compress(b"hello world " * 300) + c.flush(zlib.Z_FINISH) + b"trailing garbage"
+    add("end of stream, trailing bytes", s, [(x, rng.choice(rooms), SYNC) for x in range(1, len(s) + 1, 3)])
+    kat = max((bytes.fromhex(v["in"]) for v in kat_vectors()["vectors"] if v["expect"] == "ok"), key=len)
+    add("KAT a byte at a time", kat, [(k, 1024, SYNC) for k in range(1, len(kat) + 1)])
+    s = connection_stream(msgs_of("json", [3000, 50, 8000, 0, 700], seed=3), level=6, mem=4)
+    cut = sorted(rng.randrange(0, len(s) + 1) for _ in range(R))
+    add("every Flush value", s, [(cut[i], rng.choice([1 << 16, 500, 3]), ALL_FLUSHES[i % 7]) for i in range(R)])
+    s = connection_stream(msgs_of("corpus1", [20000], seed=5), level=9, mem=9)
+    add("room 1", s, [(len(s), 1, SYNC)] * R)
+    # inflate_batch packs inputs at up256(n + 64) and outputs at up256(cap)
+    s = connection_stream(msgs_of("json", [9000] * 6, seed=65 + seed), level=6, mem=4)
+    add("packing edges", s, offering_calls(s, 15, R, [0, 1, 191, 192, 193], [255, 256, 257]))
+    for k in range(16 - len(plans)):
+        s = connection_stream(msgs_of("json", [rng.choice(sizes) for _ in range(12)], seed=70 + 7 * seed + k), level=6,
+                              mem=4)
+        add(f"json random cuts {k}", s, cuts(s))
+    assert len(plans) == 16 and all(len(p[2]) == R for _, p in plans)
+    # what the names promise, on the oracle's records
+    recs = {name: oracle_records(p) for name, p in plans}
+    for k in range(2):
+        assert calls_after(recs[f"bit flip {k}"], is_error) >= R // 4, (k, [r[0] for r in recs[f"bit flip {k}"]])
+    eos = O.ERROR_CODES["end_of_stream"]
+    assert calls_after(recs["end of stream, trailing bytes"], lambda st: st == eos) >= R // 4
+    edges = dict(plans)["packing edges"]
+    offered = {(c[0] - (recs["packing edges"][i - 1][6] if i else 0), c[1]) for i, c in enumerate(edges[2])}
+    assert offered >= {(n, room) for n in (0, 1, 191, 192, 193) for room in (255, 256, 257)}, sorted(offered)
+    _PLANS[key] = plans
+    return plans
+
+
+def run_lockstep(make, plans, max_calls, L, timeout=60.0):
+    """K connections in lockstep.  plans: K of (stream, windowBits, R calls).
+    The oracle's records of every plan come first (main thread).  Then the
+    batcher is set to max_calls with a 5 s delay -- a ceiling a leader waits
+    out only when fewer than max_calls calls arrive -- and K threads each
+    create their inflater (make(wbits)) and make their R calls, all meeting
+    at a barrier before every call, so each round's K calls run as
+    ceil(K / max_calls) full batches.  Workers record and never assert; an
+    exception breaks the barrier for all.  Every call of every stream is then
+    compared with the oracle over all of FIELDS.  L: the library
+    (bpmd_stream_batching, bpmd_stream_batch_stats).  Returns the stats
+    [inflate calls, inflate launches, deflate flushes, deflate launches]."""
+    import threading
+    K = len(plans)
+    want = [oracle_records(p) for p in plans]
+    bar = threading.Barrier(K)
+    got, errs = [None] * K, []
+
+    def work(i):
+        stream, wbits, calls = plans[i]
+        inf = None
+        try:
+            inf = make(wbits)
+            got[i] = drive(inf, stream, calls, stop=False, before=lambda: bar.wait(timeout))
+        except BaseException as e:   # noqa: BLE001 (reported after the join)
+            errs.append((i, repr(e)))
+            bar.abort()
+        finally:
+            close = getattr(inf, "close", None)
+            if close:
+                close()
+
+    stats = (ctypes.c_ulonglong * 4)()
+    assert L.bpmd_stream_batching(max_calls, 5_000_000) == 0
+    try:
+        assert L.bpmd_stream_batch_stats(stats, 1) == 0
+        ts = [threading.Thread(target=work, args=(i,)) for i in range(K)]
+        for t in ts:
+            t.start()
+        for t in ts:
+            t.join()
+        assert L.bpmd_stream_batch_stats(stats, 1) == 0
+    finally:
+        L.bpmd_stream_batching(256, 0)
+    assert not errs, errs
+    for i in range(K):
+        assert_records_equal(got[i], want[i], plans[i][2], label=f"stream {i}")
+    return list(stats)
