@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "../../include/beast_pmd.h"
+#include "pmd_internal.h"
 
 namespace {
 
@@ -89,8 +90,6 @@ struct bpmd_batcher {
     int error = 0;
     std::thread launcher, completer;
 };
-
-extern "C" void bpmd_internal_scratch_release(hipStream_t stream);
 
 namespace {
 

@@ -11,63 +11,10 @@
 
 #include "../../include/beast_pmd.h"
 
-extern "C" int bpmd_internal_init_fixed(void);
-extern "C" int bpmd_internal_inflate_keyed(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,
-                                           uint32_t n, uint8_t* out, const uint64_t* out_off, const uint32_t* out_cap,
-                                           uint32_t* out_len, int32_t* status, uint32_t raw, const uint32_t* mask_key,
-                                           hipStream_t stream);
+#include "inflate_plan.h"
+#include "pmd_internal.h"
 
-extern "C" int bpmd_internal_inflate_keyed_split(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,
-                                                 uint32_t n, uint8_t* out, const uint64_t* out_off,
-                                                 const uint32_t* out_cap, uint32_t* out_len, int32_t* status,
-                                                 uint32_t raw, const uint32_t* mask_key, uint32_t min_in,
-                                                 hipStream_t stream);
-extern "C" int bpmd_internal_inflate_lane3(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint32_t n,
-                                           uint8_t* out, const uint64_t* out_off, const uint32_t* out_cap,
-                                           uint32_t* out_len, int32_t* status, uint32_t raw, const uint32_t* mask_key,
-                                           const uint32_t* hist_len, uint32_t hist_max, uint32_t max_in,
-                                           const uint32_t* order, uint32_t* qctr, uint32_t grid_wgs,
-                                           const uint32_t* skip, hipStream_t stream);
-extern "C" const uint32_t* bpmd_internal_lane_order(const uint32_t* in_len, uint32_t n, hipStream_t stream,
-                                                    const uint32_t** keys_out);
-extern "C" const uint32_t* bpmd_internal_lane_long_split(const uint32_t* in_len, const uint32_t* keys, uint32_t n,
-                                                         uint32_t lanes, uint32_t min_thr, uint32_t share_pct,
-                                                         hipStream_t stream);
-extern "C" int bpmd_internal_inflate_bp(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint32_t n,
-                                        uint8_t* out, const uint64_t* out_off, const uint32_t* out_cap,
-                                        uint32_t* out_len, int32_t* status, uint32_t raw, const uint32_t* order,
-                                        const uint32_t* nlong, hipStream_t s);
-extern "C" void bpmd_internal_bp_release(hipStream_t s);
-extern "C" int bpmd_internal_bp_reserve(hipStream_t s, unsigned long long in_bytes, unsigned long long out_bytes,
-                                        unsigned long long msgs);
-extern "C" int bpmd_internal_inflate_wave_ordered(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,
-                                                  uint32_t n, uint8_t* out, const uint64_t* out_off,
-                                                  const uint32_t* out_cap, uint32_t* out_len, int32_t* status,
-                                                  uint32_t raw, const uint32_t* mask_key, const uint32_t* order,
-                                                  const uint32_t* limit, hipStream_t stream);
-extern "C" int bpmd_internal_deflate_keyed(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,
-                                           uint32_t n, uint8_t* out, const uint64_t* out_off, const uint32_t* out_cap,
-                                           uint32_t* out_len, int32_t* status, int level, int window_bits,
-                                           int strategy, const uint32_t* mask_key, hipStream_t stream);
-
-extern "C" int bpmd_internal_deflate_exact(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,
-                                           uint32_t n, uint8_t* out, const uint64_t* out_off,
-                                           const uint32_t* out_cap, uint32_t* out_len, int32_t* status, int level,
-                                           int window_bits, int mem_level, int strategy, const uint32_t* mask_key,
-                                           hipStream_t stream);
-
-extern "C" int bpmd_internal_deflate_takeover(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,
-                                              uint32_t n, uint8_t* out, const uint64_t* out_off,
-                                              const uint32_t* out_cap, uint32_t* out_len, int32_t* status, int level,
-                                              int window_bits, int strategy, const uint32_t* hist_len,
-                                              hipStream_t stream);
-
-extern "C" int bpmd_internal_mask(uint8_t* data, const uint64_t* off, const uint32_t* len, uint32_t n,
-                                  const uint32_t* key, const uint8_t* phase, hipStream_t stream);
-extern "C" int bpmd_internal_utf8(const uint8_t* data, const uint64_t* off, const uint32_t* len, uint32_t n,
-                                  int32_t* result, const uint8_t* text, int32_t fail_status, hipStream_t stream);
-extern "C" int bpmd_internal_slide(uint8_t* buf, const uint64_t* base, const uint32_t* pos, const uint32_t* keep,
-                                   uint32_t n, hipStream_t stream);
+using namespace bpmd;
 
 namespace {
 std::mutex g_init_mu;
@@ -129,8 +76,11 @@ bool side_for(hipStream_t s, Side& out)
     out = d;
     return true;
 }
+}  // namespace
 
-std::mutex* stream_mutex(hipStream_t s)
+// the launch lock of a stream (pmd_multi.hip takes it around its own
+// scratch use, as scratch_block requires)
+std::mutex* bpmd::stream_mutex(hipStream_t s)
 {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return nullptr;
@@ -144,7 +94,7 @@ std::mutex* stream_mutex(hipStream_t s)
 
 // the caller holds the stream's launch lock, so nothing else enqueues work
 // that could use the block while it is replaced
-uint8_t* scratch_for(hipStream_t s, size_t bytes, int which = 0)
+uint8_t* bpmd::scratch_block(hipStream_t s, size_t bytes, ScratchSlot which)
 {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return nullptr;
@@ -177,25 +127,14 @@ uint8_t* scratch_for(hipStream_t s, size_t bytes, int which = 0)
     g_scratch.push_back(Scratch{dev, s, which, p, bytes});
     return p;
 }
-}
-
-// scratch block `which` (0 inflate queue, 1-2 deflate workspace, 3-4 exact
-// deflate queue and workspace, 5 inflate message order, 6 wave inflate queue,
-// 7 deflate chunk queue, 8 multi-device output totals, 9 long-payload split,
-// 10-11 block-parallel inflate stats and decode workspace)
-// for other translation units
-extern "C" void* bpmd_internal_scratch(hipStream_t s, size_t bytes, int which)
-{
-    return scratch_for(s, bytes, which);
-}
 
 // A small pinned host block per (device, stream, which) -- the target of a
-// read-back that an event then covers (0: the deflate chunk count).  Kept
+// read-back that an event then covers.  Kept
 // per stream, not per host thread: pmd_multi.hip launches each shard from a
 // thread of its own, and a thread_local block would leak one pinned
 // allocation per shard thread.  The caller holds the stream's
 // launch lock; freed by bpmd_internal_scratch_release.
-extern "C" void* bpmd_internal_pinned(hipStream_t s, size_t bytes, int which)
+void* bpmd::pinned_block(hipStream_t s, size_t bytes, PinnedSlot which)
 {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || bytes > 4096) return nullptr;
@@ -220,7 +159,7 @@ extern "C" void bpmd_internal_scratch_release(hipStream_t s)
 {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return;
-    bpmd_internal_bp_release(s);
+    bp_release(s);
     hipStream_t side = nullptr;
     {
     std::lock_guard<std::mutex> lk(g_scratch_mu);
@@ -261,14 +200,10 @@ extern "C" void bpmd_internal_scratch_release(hipStream_t s)
         }
     }
     if (side) {
-        bpmd_internal_bp_release(side);
+        bp_release(side);
         (void)hipStreamDestroy(side);
     }
 }
-
-// the launch lock of a stream (pmd_multi.hip takes it around its own
-// scratch use, as scratch_for requires)
-extern "C" void* bpmd_internal_stream_mutex(hipStream_t s) { return stream_mutex(s); }
 
 // Number of scratch blocks held (footprint tests)
 extern "C" size_t bpmd_internal_scratch_count(void)
@@ -284,10 +219,7 @@ extern "C" const char* bpmd_version(void) { return "beast_pmd 0.2 (gfx950)"; }
 extern "C" unsigned bpmd_diag_grid_override = 0;
 extern "C" void bpmd_diag_set_grid(unsigned grid) { bpmd_diag_grid_override = grid; }
 
-// Kernel choice for a batch: one lane per message (pmd_inflate_lane3.hip)
-// for throughput, one wave per message (pmd_inflate.hip) for latency when
-// the batch is too small to fill the chip's lanes, and block-parallel decode
-// (pmd_inflate_bp.hip) for the long payloads of large batches.
+// Kernel choice for a batch: inflate_plan.h.
 // BPMD_INFLATE=lane|wave|bp or bpmd_set_inflate_kernel() forces one (the
 // tests run all three; "bp" sends every payload of 64 bytes or more through
 // the block-parallel path).
@@ -311,27 +243,6 @@ static int inflate_mode()
     return m;
 }
 
-// block-parallel decode of long payloads in automatic mode (BPMD_INFLATE_BP=0: off)
-static bool inflate_bp_enabled()
-{
-    static const bool on = [] {
-        const char* e = getenv("BPMD_INFLATE_BP");
-        return !(e && e[0] == '0');
-    }();
-    return on;
-}
-
-// Automatic choice, per message: a lane-kernel wave lasts as long as its
-// longest message and a batch of few messages leaves most lanes of the chip
-// idle, so payloads longer than the split (compressed bytes; several 4 KiB
-// chunks of output) go to the wave kernel and only batches of >= 2048
-// messages use lanes at all; batches of >= 32 Ki messages use lanes only.  BPMD_INFLATE_SPLIT overrides the split.
-static uint32_t inflate_split()
-{
-    const char* e = getenv("BPMD_INFLATE_SPLIT");
-    return e ? (uint32_t)strtoul(e, nullptr, 10) : 4096u;
-}
-
 extern "C" int bpmd_init(void)
 {
     int dev = -1;
@@ -341,7 +252,7 @@ extern "C" int bpmd_init(void)
     std::lock_guard<std::mutex> lk(g_init_mu);
     const uint64_t bit = dev < 64 ? 1ull << dev : 0ull;
     if (g_init_devices & bit) return BPMD_R_OK;
-    if (bpmd_internal_init_fixed() != 0) return BPMD_R_HIP_ERROR;
+    if (init_fixed() != 0) return BPMD_R_HIP_ERROR;
     g_init_devices |= bit;
     return BPMD_R_OK;
 }
@@ -359,8 +270,7 @@ extern "C" int bpmd_inflate_reserve(void* stream, uint64_t in_bytes, uint64_t ou
     std::lock_guard<std::mutex> launch(*mu);
     Side sd;
     if (!side_for(s, sd)) return BPMD_R_HIP_ERROR;
-    if (bpmd_internal_bp_reserve(s, in_bytes, out_bytes, n_long) ||
-        bpmd_internal_bp_reserve(sd.side, in_bytes, out_bytes, n_long))
+    if (bp_reserve(s, in_bytes, out_bytes, n_long) || bp_reserve(sd.side, in_bytes, out_bytes, n_long))
         return BPMD_R_HIP_ERROR;
     return BPMD_R_OK;
 }
@@ -373,19 +283,22 @@ extern "C" size_t bpmd_deflate_upper_bound(size_t n)
 
 namespace {
 
+bool batch_has_nulls(const Batch& b)
+{
+    return !b.in || !b.in_off || !b.in_len || !b.out || !b.out_off || !b.out_cap || !b.out_len || !b.status;
+}
+
 // bpmd_inflate_batch and its fused / context-takeover forms.  key: masking
 // keys or null; hist: window bytes before each slot (context takeover) or
-// null -- only the lane kernel reads a window, so it always runs then.
-int inflate_impl(const bpmd_cfg* cfg, const uint8_t* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len,
-                 uint32_t n_msgs, uint8_t* d_out, const uint64_t* d_out_off, const uint32_t* d_out_cap,
-                 uint32_t* d_out_len, int32_t* d_status, const uint32_t* key, const uint32_t* hist, void* stream)
+// null.  inflate_plan.h decides which decoder takes which messages; this
+// enqueues the plan's steps in order and returns at the first error.
+int inflate_impl(const bpmd_cfg* cfg, const Batch& b, const uint32_t* key, const uint32_t* hist, void* stream)
 {
     if (!cfg) return BPMD_R_INVALID_ARGUMENT;
     // inflate_stream.ipp:57-61: windowBits outside 8..15 throws domain_error
     if (cfg->window_bits < 8 || cfg->window_bits > 15) return BPMD_R_DOMAIN_ERROR;
-    if (n_msgs == 0) return BPMD_R_OK;
-    if (!d_in || !d_in_off || !d_in_len || !d_out || !d_out_off || !d_out_cap || !d_out_len || !d_status)
-        return BPMD_R_INVALID_ARGUMENT;
+    if (b.n == 0) return BPMD_R_OK;
+    if (batch_has_nulls(b)) return BPMD_R_INVALID_ARGUMENT;
     int r = bpmd_init();
     if (r) return r;
     const uint32_t raw = (cfg->flags & BPMD_F_RAW) ? 1u : 0u;
@@ -393,131 +306,61 @@ int inflate_impl(const bpmd_cfg* cfg, const uint8_t* d_in, const uint64_t* d_in_
     std::mutex* mu = stream_mutex(s);
     if (!mu) return BPMD_R_HIP_ERROR;
     std::lock_guard<std::mutex> launch(*mu);
-    const int m = inflate_mode();
-    // block-parallel decode applies to plain batches (no takeover window, no
-    // masking key: the segment decoder starts mid-payload)
-    const bool bp_ok = !hist && !key && ((m == 0 && inflate_bp_enabled()) || m == 3);
-    if (m == 3 && bp_ok) {
-        // forced (tests): every payload of 64 bytes or more, the rest on lanes
-        const uint32_t* keys = nullptr;
-        const uint32_t* order = bpmd_internal_lane_order(d_in_len, n_msgs, s, &keys);
-        const uint32_t* nlong = order ? bpmd_internal_lane_long_split(d_in_len, keys, n_msgs, 0u, 64u, 0u, s) : nullptr;
-        if (!nlong || bpmd_internal_inflate_bp(d_in, d_in_off, d_in_len, n_msgs, d_out, d_out_off, d_out_cap,
-                                               d_out_len, d_status, raw, order, nlong, s) ||
-            bpmd_internal_inflate_lane3(d_in, d_in_off, d_in_len, n_msgs, d_out, d_out_off, d_out_cap, d_out_len,
-                                        d_status, raw, nullptr, nullptr, 1u << cfg->window_bits, 0u, order, nullptr,
-                                        0u, nlong, s))
+    // every knob is read once, but the split (BPMD_INFLATE_SPLIT) at every call
+    static const InflateKnobs latched{env_on("BPMD_INFLATE_BP"), 0u, env_on("BPMD_INFLATE_ORDER"),
+                                      env_on("BPMD_INFLATE_LONG"), env_uint("BPMD_LONG_SHARE_PCT", 125u)};
+    InflateKnobs knobs = latched;
+    knobs.split = env_uint("BPMD_INFLATE_SPLIT", 4096u);
+    // 4 workgroups of 64 messages per CU are resident; diagnostics / tests:
+    // BPMD_QUEUE_WGS caps the grid so that small batches run through the work
+    // queue too
+    static const uint32_t q_override = env_uint("BPMD_QUEUE_WGS", 0u);
+    const uint32_t wgs = q_override ? q_override : 4u * (uint32_t)cu_count();
+    const InflatePlan p = plan_inflate(inflate_mode(), b.n, hist != nullptr, key != nullptr, wgs, knobs);
+
+    uint32_t* qctr = nullptr;
+    const uint32_t *order = nullptr, *keys = nullptr, *nlong = nullptr;
+    if (p.queue) {
+        qctr = (uint32_t*)scratch_block(s, 256, SCR_INFLATE_QUEUE);
+        if (!qctr || hipMemsetAsync(qctr, 0, sizeof(uint32_t), s) != hipSuccess) return BPMD_R_HIP_ERROR;
+    }
+    if (p.order && !(order = lane_order(b.in_len, b.n, s, &keys))) return BPMD_R_HIP_ERROR;
+    if (p.longs != InflatePlan::LONG_NONE &&
+        !(nlong = bpmd_internal_lane_long_split(b.in_len, keys, b.n, p.split_lanes, p.split_min_thr, p.split_share_pct,
+                                                s)))
+        return BPMD_R_HIP_ERROR;
+    // the long payloads.  On the side stream they decode block-parallel while
+    // the lane kernel runs the rest on the caller's stream (it skips the long
+    // prefix of the order): each fills the CUs the other's tail leaves idle.
+    // (Both enqueue only, except the stream's first block-parallel call
+    // without bpmd_inflate_reserve: it reads its workspace totals back once,
+    // on the side stream, so it waits for the work queued before it -- and
+    // cannot run under stream capture)
+    Side sd;
+    int e_side = 0;
+    if (p.longs == InflatePlan::LONG_BP_INLINE) {
+        if (inflate_bp(b, raw, order, nlong, s)) return BPMD_R_HIP_ERROR;
+    } else if (p.longs == InflatePlan::LONG_BP_SIDE) {
+        if (!side_for(s, sd) || hipEventRecord(sd.fork, s) != hipSuccess ||
+            hipStreamWaitEvent(sd.side, sd.fork, 0) != hipSuccess)
             return BPMD_R_HIP_ERROR;
-        return BPMD_R_OK;
+        e_side = inflate_bp(b, raw, order, nlong, sd.side);
+    } else if (p.longs == InflatePlan::LONG_WAVE_ORDERED) {
+        if (inflate_wave_ordered(b, raw, key, order, nlong, s)) return BPMD_R_HIP_ERROR;
     }
-    // lane-kernel share: everything (hist / forced lane), nothing (forced wave /
-    // small batch), or the payloads of at most `split` bytes
-    const bool lane = hist || m == 1 || (m == 0 && n_msgs >= 2048);
-    // from 32 Ki messages on, the lanes fill the chip whatever the sizes: no
-    // split, and no second launch (C2 +1.6 %, C4 lane-only 23.2 vs 22.6 GiB/s)
-    const uint32_t split = (hist || m != 0 || n_msgs >= 32768) ? 0u : inflate_split();
     int e = 0;
-    if (lane) {
-        // more messages than the chip holds lanes: a work queue keeps every
-        // lane busy until the batch is done (mixed sizes, configs[3])
-        int dev = 0, cus = 256;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        uint32_t wgs = 4u * (uint32_t)cus;   // 4 workgroups of 64 messages per CU are resident
-        // diagnostics / tests: BPMD_QUEUE_WGS caps the grid so that small batches
-        // run through the work queue too
-        static const uint32_t q_override = [] {
-            const char* e = getenv("BPMD_QUEUE_WGS");
-            return e ? (uint32_t)strtoul(e, nullptr, 10) : 0u;
-        }();
-        if (q_override) wgs = q_override;
-        uint32_t* qctr = nullptr;
-        const uint32_t* order = nullptr;
-        const uint32_t* nlong = nullptr;
-        if (n_msgs > wgs * 64u && !split) {
-            qctr = (uint32_t*)scratch_for(s, 256);
-            if (!qctr || hipMemsetAsync(qctr, 0, sizeof(uint32_t), s) != hipSuccess) return BPMD_R_HIP_ERROR;
-            // longest first, so no lane starts a long message as the batch drains
-            // (BPMD_INFLATE_ORDER=0: batch order)
-            static const bool ordered = [] {
-                const char* e = getenv("BPMD_INFLATE_ORDER");
-                return !(e && e[0] == '0');
-            }();
-            // payloads too long for one lane go to the wave kernel first
-            // (automatic mode, no takeover window; BPMD_INFLATE_LONG=0: off)
-            static const bool long_split = [] {
-                const char* e = getenv("BPMD_INFLATE_LONG");
-                return !(e && e[0] == '0');
-            }();
-            const uint32_t* keys = nullptr;
-            if (ordered && !(order = bpmd_internal_lane_order(d_in_len, n_msgs, s, &keys))) return BPMD_R_HIP_ERROR;
-            if (ordered && long_split && m == 0 && !hist) {
-                // long payloads: block-parallel, or one wave each
-                // (block-parallel: above 1.25 lanes' share of the batch, from 2 KiB
-                // compressed; DESIGN.md 4.1c.  One 8-way C4 shard at 50 / 100 /
-                // 150 / 200 %: 9.2 / 8.4-8.9 / 8.3 / 10.5 ms; C4 projected 4- and
-                // 8-way speedups at 100 / 125 / 150 %: 3.29-3.30 and 5.29 / 3.36-3.46
-                // and 5.30-5.36 / 2.81-2.95 and 5.39-5.45, round 4)
-                static const uint32_t share_pct = [] {
-                    const char* e = getenv("BPMD_LONG_SHARE_PCT");
-                    return e ? (uint32_t)strtoul(e, nullptr, 10) : 125u;
-                }();
-                if (!(nlong = bp_ok ? bpmd_internal_lane_long_split(d_in_len, keys, n_msgs, wgs * 64u, 2048u, share_pct, s)
-                                    : bpmd_internal_lane_long_split(d_in_len, keys, n_msgs, wgs * 64u, 4096u, 200u, s)))
-                    return BPMD_R_HIP_ERROR;
-                if (bp_ok) {
-                    // the lane kernel on the caller's stream (it skips the long
-                    // prefix of the order) and the long payloads block-parallel
-                    // on the side stream at the same time: each fills the CUs
-                    // the other's tail leaves idle
-                    Side sd;
-                    if (!side_for(s, sd) || hipEventRecord(sd.fork, s) != hipSuccess ||
-                        hipStreamWaitEvent(sd.side, sd.fork, 0) != hipSuccess)
-                        return BPMD_R_HIP_ERROR;
-                    // (both enqueue only, except the stream's first
-                    // block-parallel call without bpmd_inflate_reserve: it
-                    // reads its workspace totals back once, on the side
-                    // stream, so it waits for the work queued before it --
-                    // and cannot run under stream capture)
-                    const int eb = bpmd_internal_inflate_bp(d_in, d_in_off, d_in_len, n_msgs, d_out, d_out_off,
-                                                            d_out_cap, d_out_len, d_status, raw, order, nlong, sd.side);
-                    e = bpmd_internal_inflate_lane3(d_in, d_in_off, d_in_len, n_msgs, d_out, d_out_off, d_out_cap,
-                                                    d_out_len, d_status, raw, key, hist, 1u << cfg->window_bits, 0u,
-                                                    order, qctr, wgs, nlong, s);
-                    if (hipEventRecord(sd.join, sd.side) != hipSuccess || hipStreamWaitEvent(s, sd.join, 0) != hipSuccess)
-                        return BPMD_R_HIP_ERROR;
-                    return e || eb ? BPMD_R_HIP_ERROR : BPMD_R_OK;
-                }
-                if (bpmd_internal_inflate_wave_ordered(d_in, d_in_off, d_in_len, n_msgs, d_out, d_out_off, d_out_cap,
-                                                       d_out_len, d_status, raw, key, order, nlong, s))
-                    return BPMD_R_HIP_ERROR;
-            }
-        } else if (split && bp_ok) {
-            // payloads over the split: block-parallel; the rest on lanes, in
-            // the same longest-first order after them
-            const uint32_t* keys = nullptr;
-            if (!(order = bpmd_internal_lane_order(d_in_len, n_msgs, s, &keys)) ||
-                !(nlong = bpmd_internal_lane_long_split(d_in_len, keys, n_msgs, 0u, split, 0u, s)) ||
-                bpmd_internal_inflate_bp(d_in, d_in_off, d_in_len, n_msgs, d_out, d_out_off, d_out_cap, d_out_len,
-                                         d_status, raw, order, nlong, s))
-                return BPMD_R_HIP_ERROR;
-            e = bpmd_internal_inflate_lane3(d_in, d_in_off, d_in_len, n_msgs, d_out, d_out_off, d_out_cap, d_out_len,
-                                            d_status, raw, key, hist, 1u << cfg->window_bits, 0u, order, nullptr, wgs,
-                                            nlong, s);
-            return e ? BPMD_R_HIP_ERROR : BPMD_R_OK;
-        }
-        e = bpmd_internal_inflate_lane3(d_in, d_in_off, d_in_len, n_msgs, d_out, d_out_off, d_out_cap, d_out_len,
-                                        d_status, raw, key, hist, 1u << cfg->window_bits, split, order, qctr, wgs,
-                                        nlong, s);
+    if (p.lanes != InflatePlan::LANES_NONE)
+        e = inflate_lane3(b, raw, key, hist, 1u << cfg->window_bits, p.max_in, order, qctr, wgs, nlong, s);
+    if (p.longs == InflatePlan::LONG_BP_SIDE) {
+        if (hipEventRecord(sd.join, sd.side) != hipSuccess || hipStreamWaitEvent(s, sd.join, 0) != hipSuccess)
+            return BPMD_R_HIP_ERROR;
+        e = e || e_side;
     }
-    if (!e && (!lane || split))
-        e = bpmd_internal_inflate_keyed_split(d_in, d_in_off, d_in_len, n_msgs, d_out, d_out_off, d_out_cap,
-                                              d_out_len, d_status, raw, key, lane ? split : 0u, s);
+    if (!e && p.wave != InflatePlan::WAVE_NONE) e = inflate_keyed_split(b, raw, key, p.min_in, s);
     return e ? BPMD_R_HIP_ERROR : BPMD_R_OK;
 }
 
-int deflate_impl(const bpmd_cfg* cfg, const uint8_t* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len,
-                 uint32_t n_msgs, uint8_t* d_out, const uint64_t* d_out_off, const uint32_t* d_out_cap,
-                 uint32_t* d_out_len, int32_t* d_status, const uint32_t* key, const uint32_t* hist, void* stream)
+int deflate_impl(const bpmd_cfg* cfg, const Batch& b, const uint32_t* key, const uint32_t* hist, void* stream)
 {
     if (!cfg) return BPMD_R_INVALID_ARGUMENT;
     // deflate_stream.ipp:235-253: level -1 means 6; windowBits 8 becomes 9;
@@ -528,29 +371,21 @@ int deflate_impl(const bpmd_cfg* cfg, const uint8_t* d_in, const uint64_t* d_in_
     if (level < 0 || level > 9 || wbits < 8 || wbits > 15 || cfg->mem_level < 1 || cfg->mem_level > 9)
         return BPMD_R_INVALID_ARGUMENT;
     if (cfg->strategy < BPMD_STRATEGY_NORMAL || cfg->strategy > BPMD_STRATEGY_FIXED) return BPMD_R_INVALID_ARGUMENT;
-    if (n_msgs == 0) return BPMD_R_OK;
-    if (!d_in || !d_in_off || !d_in_len || !d_out || !d_out_off || !d_out_cap || !d_out_len || !d_status)
-        return BPMD_R_INVALID_ARGUMENT;
+    if (b.n == 0) return BPMD_R_OK;
+    if (batch_has_nulls(b)) return BPMD_R_INVALID_ARGUMENT;
     int r = bpmd_init();
     if (r) return r;
-    std::mutex* mu = stream_mutex((hipStream_t)stream);
+    const hipStream_t s = (hipStream_t)stream;
+    std::mutex* mu = stream_mutex(s);
     if (!mu) return BPMD_R_HIP_ERROR;
     std::lock_guard<std::mutex> launch(*mu);
     if (cfg->flags & BPMD_F_EXACT) {
         // the reference's own algorithm, message by message (pmd_deflate_exact.hip)
         if (hist) return BPMD_R_INVALID_ARGUMENT;
-        return bpmd_internal_deflate_exact(d_in, d_in_off, d_in_len, n_msgs, d_out, d_out_off, d_out_cap, d_out_len,
-                                           d_status, level, wbits, cfg->mem_level, cfg->strategy, key,
-                                           (hipStream_t)stream)
-                   ? BPMD_R_HIP_ERROR
-                   : BPMD_R_OK;
+        return deflate_exact(b, level, wbits, cfg->mem_level, cfg->strategy, key, s) ? BPMD_R_HIP_ERROR : BPMD_R_OK;
     }
-    int e = hist ? bpmd_internal_deflate_takeover(d_in, d_in_off, d_in_len, n_msgs, d_out, d_out_off, d_out_cap,
-                                                  d_out_len, d_status, level, wbits, cfg->strategy, hist,
-                                                  (hipStream_t)stream)
-                 : bpmd_internal_deflate_keyed(d_in, d_in_off, d_in_len, n_msgs, d_out, d_out_off, d_out_cap,
-                                               d_out_len, d_status, level, wbits, cfg->strategy, key,
-                                               (hipStream_t)stream);
+    int e = hist ? deflate_takeover(b, level, wbits, cfg->strategy, hist, s)
+                 : deflate_keyed(b, level, wbits, cfg->strategy, key, s);
     return e ? BPMD_R_HIP_ERROR : BPMD_R_OK;
 }
 
@@ -561,8 +396,8 @@ extern "C" int bpmd_inflate_batch(const bpmd_cfg* cfg, const uint8_t* d_in, cons
                                   const uint64_t* d_out_off, const uint32_t* d_out_cap,
                                   uint32_t* d_out_len, int32_t* d_status, void* stream)
 {
-    return inflate_impl(cfg, d_in, d_in_off, d_in_len, n_msgs, d_out, d_out_off, d_out_cap, d_out_len, d_status,
-                        nullptr, nullptr, stream);
+    const Batch b{d_in, d_in_off, d_in_len, n_msgs, d_out, d_out_off, d_out_cap, d_out_len, d_status};
+    return inflate_impl(cfg, b, nullptr, nullptr, stream);
 }
 
 extern "C" int bpmd_deflate_batch(const bpmd_cfg* cfg, const uint8_t* d_in, const uint64_t* d_in_off,
@@ -570,8 +405,8 @@ extern "C" int bpmd_deflate_batch(const bpmd_cfg* cfg, const uint8_t* d_in, cons
                                   const uint64_t* d_out_off, const uint32_t* d_out_cap,
                                   uint32_t* d_out_len, int32_t* d_status, void* stream)
 {
-    return deflate_impl(cfg, d_in, d_in_off, d_in_len, n_msgs, d_out, d_out_off, d_out_cap, d_out_len, d_status,
-                        nullptr, nullptr, stream);
+    const Batch b{d_in, d_in_off, d_in_len, n_msgs, d_out, d_out_off, d_out_cap, d_out_len, d_status};
+    return deflate_impl(cfg, b, nullptr, nullptr, stream);
 }
 
 // ------------------------------------------------ frame passes (§8(f) N1)
@@ -583,14 +418,9 @@ extern "C" int bpmd_mask_batch(uint8_t* d_data, const uint64_t* d_off, const uin
     if (!d_data || !d_off || !d_len || !d_key) return BPMD_R_INVALID_ARGUMENT;
     int r = bpmd_init();
     if (r) return r;
-    return bpmd_internal_mask(d_data, d_off, d_len, n_msgs, d_key, d_phase, (hipStream_t)stream) ? BPMD_R_HIP_ERROR
+    return launch_mask(d_data, d_off, d_len, n_msgs, d_key, d_phase, (hipStream_t)stream) ? BPMD_R_HIP_ERROR
                                                                                                  : BPMD_R_OK;
 }
-
-extern "C" int bpmd_internal_frame(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, const uint8_t* op,
-                                   const uint8_t* flags, const uint32_t* keys, const uint32_t* key_base,
-                                   uint32_t frame_max, uint32_t n, uint8_t* wire, const uint64_t* wire_off,
-                                   hipStream_t stream);
 
 // frame.hpp:134-175 header sizes over the write.hpp:463-545 frame loop
 extern "C" uint64_t bpmd_frame_wire_size(uint64_t payload_len, uint32_t frame_max, int masked)
@@ -612,7 +442,7 @@ extern "C" int bpmd_frame_batch(const uint8_t* d_in, const uint64_t* d_in_off, c
         return BPMD_R_INVALID_ARGUMENT;
     int r = bpmd_init();
     if (r) return r;
-    return bpmd_internal_frame(d_in, d_in_off, d_in_len, d_op, d_flags, d_keys, d_key_base, frame_max, n_msgs, d_wire,
+    return launch_frame(d_in, d_in_off, d_in_len, d_op, d_flags, d_keys, d_key_base, frame_max, n_msgs, d_wire,
                                d_wire_off, (hipStream_t)stream)
                ? BPMD_R_HIP_ERROR
                : BPMD_R_OK;
@@ -625,7 +455,7 @@ extern "C" int bpmd_utf8_check_batch(const uint8_t* d_data, const uint64_t* d_of
     if (!d_data || !d_off || !d_len || !d_result) return BPMD_R_INVALID_ARGUMENT;
     int r = bpmd_init();
     if (r) return r;
-    return bpmd_internal_utf8(d_data, d_off, d_len, n_msgs, d_result, nullptr, 0, (hipStream_t)stream)
+    return launch_utf8(d_data, d_off, d_len, n_msgs, d_result, nullptr, 0, (hipStream_t)stream)
                ? BPMD_R_HIP_ERROR
                : BPMD_R_OK;
 }
@@ -635,11 +465,11 @@ extern "C" int bpmd_read_batch(const bpmd_cfg* cfg, const uint8_t* d_in, const u
                                uint32_t n_msgs, uint8_t* d_out, const uint64_t* d_out_off,
                                const uint32_t* d_out_cap, uint32_t* d_out_len, int32_t* d_status, void* stream)
 {
-    int r = inflate_impl(cfg, d_in, d_in_off, d_in_len, n_msgs, d_out, d_out_off, d_out_cap, d_out_len, d_status,
-                         d_key, nullptr, stream);
+    const Batch b{d_in, d_in_off, d_in_len, n_msgs, d_out, d_out_off, d_out_cap, d_out_len, d_status};
+    int r = inflate_impl(cfg, b, d_key, nullptr, stream);
     if (r || n_msgs == 0 || !d_text) return r;
     // read.hpp:1372-1384: text whose inflated bytes are not UTF-8 fails with bad_frame_payload
-    return bpmd_internal_utf8(d_out, d_out_off, d_out_len, n_msgs, d_status, d_text, BPMD_BAD_FRAME_PAYLOAD,
+    return launch_utf8(d_out, d_out_off, d_out_len, n_msgs, d_status, d_text, BPMD_BAD_FRAME_PAYLOAD,
                               (hipStream_t)stream)
                ? BPMD_R_HIP_ERROR
                : BPMD_R_OK;
@@ -650,8 +480,8 @@ extern "C" int bpmd_write_batch(const bpmd_cfg* cfg, const uint8_t* d_in, const 
                                 const uint64_t* d_out_off, const uint32_t* d_out_cap, uint32_t* d_out_len,
                                 int32_t* d_status, void* stream)
 {
-    return deflate_impl(cfg, d_in, d_in_off, d_in_len, n_msgs, d_out, d_out_off, d_out_cap, d_out_len, d_status,
-                        d_key, nullptr, stream);
+    const Batch b{d_in, d_in_off, d_in_len, n_msgs, d_out, d_out_off, d_out_cap, d_out_len, d_status};
+    return deflate_impl(cfg, b, d_key, nullptr, stream);
 }
 
 // ---------------------------------------------- context takeover (§8(f) N3)
@@ -661,9 +491,9 @@ extern "C" int bpmd_inflate_takeover_batch(const bpmd_cfg* cfg, const uint8_t* d
                                            uint8_t* d_out, const uint64_t* d_out_off, const uint32_t* d_out_cap,
                                            uint32_t* d_out_len, int32_t* d_status, void* stream)
 {
+    const Batch b{d_in, d_in_off, d_in_len, n_msgs, d_out, d_out_off, d_out_cap, d_out_len, d_status};
     if (n_msgs && !d_hist_len) return BPMD_R_INVALID_ARGUMENT;
-    return inflate_impl(cfg, d_in, d_in_off, d_in_len, n_msgs, d_out, d_out_off, d_out_cap, d_out_len, d_status,
-                        nullptr, d_hist_len, stream);
+    return inflate_impl(cfg, b, nullptr, d_hist_len, stream);
 }
 
 extern "C" int bpmd_deflate_takeover_batch(const bpmd_cfg* cfg, const uint8_t* d_in, const uint64_t* d_in_off,
@@ -671,9 +501,9 @@ extern "C" int bpmd_deflate_takeover_batch(const bpmd_cfg* cfg, const uint8_t* d
                                            uint8_t* d_out, const uint64_t* d_out_off, const uint32_t* d_out_cap,
                                            uint32_t* d_out_len, int32_t* d_status, void* stream)
 {
+    const Batch b{d_in, d_in_off, d_in_len, n_msgs, d_out, d_out_off, d_out_cap, d_out_len, d_status};
     if (n_msgs && !d_hist_len) return BPMD_R_INVALID_ARGUMENT;
-    return deflate_impl(cfg, d_in, d_in_off, d_in_len, n_msgs, d_out, d_out_off, d_out_cap, d_out_len, d_status,
-                        nullptr, d_hist_len, stream);
+    return deflate_impl(cfg, b, nullptr, d_hist_len, stream);
 }
 
 extern "C" int bpmd_slide_batch(uint8_t* d_buf, const uint64_t* d_base, const uint32_t* d_pos, const uint32_t* d_keep,
@@ -683,5 +513,5 @@ extern "C" int bpmd_slide_batch(uint8_t* d_buf, const uint64_t* d_base, const ui
     if (!d_buf || !d_base || !d_pos || !d_keep) return BPMD_R_INVALID_ARGUMENT;
     int r = bpmd_init();
     if (r) return r;
-    return bpmd_internal_slide(d_buf, d_base, d_pos, d_keep, n, (hipStream_t)stream) ? BPMD_R_HIP_ERROR : BPMD_R_OK;
+    return launch_slide(d_buf, d_base, d_pos, d_keep, n, (hipStream_t)stream) ? BPMD_R_HIP_ERROR : BPMD_R_OK;
 }

@@ -45,6 +45,7 @@
 #include "pmd_common.h"
 #include "wave_util.h"
 #include "lz_core.h"
+#include "pmd_internal.h"
 
 namespace bpmd {
 namespace dfl {
@@ -1667,9 +1668,6 @@ stitch_kernel(const uint32_t* __restrict__ in_len, uint32_t n, uint32_t all, con
 }  // namespace dfl
 }  // namespace bpmd
 
-extern "C" unsigned bpmd_diag_grid_override;
-extern "C" void* bpmd_internal_scratch(hipStream_t s, size_t bytes, int which);
-extern "C" void* bpmd_internal_pinned(hipStream_t s, size_t bytes, int which);
 #ifndef BPMD_DEFLATE_QUEUE
 #define BPMD_DEFLATE_QUEUE 1
 #endif
@@ -1677,23 +1675,21 @@ extern "C" void* bpmd_internal_pinned(hipStream_t s, size_t bytes, int which);
 namespace {
 // single-chunk messages: as many waves as the LDS holds, grid-strided or
 // (BPMD_DEFLATE_QUEUE) drained from a counter
-int launch_single(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint32_t n, uint8_t* out,
-                  const uint64_t* out_off, const uint32_t* out_cap, uint32_t* out_len, int32_t* status,
-                  const bpmd::dfl::Params& P, hipStream_t stream)
+int launch_single(const bpmd::Batch& b, const bpmd::dfl::Params& P, hipStream_t stream)
 {
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    const uint32_t n = b.n;
+    const unsigned cus = (unsigned)bpmd::cu_count();
     const unsigned per_cu = (160u * 1024u) / (unsigned)sizeof(bpmd::dfl::DefLds<0>);
-    unsigned grid = (unsigned)cus * (per_cu ? per_cu : 1u);
+    unsigned grid = cus * (per_cu ? per_cu : 1u);
     if (bpmd_diag_grid_override) grid = bpmd_diag_grid_override;
     if (grid > n) grid = n;
     uint32_t* qctr = nullptr;
-    if (BPMD_DEFLATE_QUEUE && n > grid) {   // scratch block 7: the single-chunk message counter
-        qctr = (uint32_t*)bpmd_internal_scratch(stream, 256, 7);
+    if (BPMD_DEFLATE_QUEUE && n > grid) {
+        qctr = (uint32_t*)bpmd::scratch_block(stream, 256, bpmd::SCR_DEFLATE_QUEUE);
         if (!qctr || hipMemsetAsync(qctr, 0, sizeof(uint32_t), stream) != hipSuccess) return (int)hipErrorOutOfMemory;
     }
-    hipLaunchKernelGGL(bpmd::dfl::deflate_kernel, dim3(grid), dim3(64), 0, stream, in, in_off, in_len, n, out, out_off,
-                       out_cap, out_len, status, P, qctr);
+    hipLaunchKernelGGL(bpmd::dfl::deflate_kernel, dim3(grid), dim3(64), 0, stream, b.in, b.in_off, b.in_len, n, b.out,
+                       b.out_off, b.out_cap, b.out_len, b.status, P, qctr);
     return (int)hipGetLastError();
 }
 }  // namespace
@@ -1704,11 +1700,10 @@ namespace {
 // the level still picks the parser, and the chain keeps the engine's caps
 // host_chunks >= 0: the caller knows the batch's chunk count (the per-stream
 // deflater, one message of known length), so nothing is read back
-int deflate_impl(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint32_t n, uint8_t* out,
-                 const uint64_t* out_off, const uint32_t* out_cap, uint32_t* out_len, int32_t* status,
-                 uint32_t* out_bits, const uint32_t* mask_key, const uint32_t* hist_len, int level, int window_bits,
-                 int strategy, hipStream_t stream, const int* tune = nullptr, int64_t host_chunks = -1)
+int deflate_impl(const bpmd::Batch& b, uint32_t* out_bits, const uint32_t* mask_key, const uint32_t* hist_len, int level,
+                 int window_bits, int strategy, hipStream_t stream, const int* tune = nullptr, int64_t host_chunks = -1)
 {
+    const auto& [in, in_off, in_len, n, out, out_off, out_cap, out_len, status] = b;
     bpmd::dfl::Params P;
     P.L = lz::level_params(level);
     auto clamp16 = [](int v) { return (uint16_t)(v < 0 ? 0 : v > 65535 ? 65535 : v); };
@@ -1733,7 +1728,7 @@ int deflate_impl(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_l
     // how many chunk blocks the large messages make (one small read back: it
     // sizes the workspace; the single-chunk kernel is enqueued right after it
     // and runs meanwhile)
-    uint32_t* d_total = (uint32_t*)bpmd_internal_scratch(stream, 256, 1);   // [0] chunk count, [32] chunk queue
+    uint32_t* d_total = (uint32_t*)bpmd::scratch_block(stream, 256, bpmd::SCR_DEFLATE_COUNT);   // [0] chunk count, [32] chunk queue
     if (!d_total) return (int)hipErrorOutOfMemory;
     // one message with its chunk count known (a stream's write): one setup
     // launch below instead of the memset, the count, the scan and the fill
@@ -1750,12 +1745,12 @@ int deflate_impl(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_l
     if (host_chunks >= 0) {
         if (host_chunks > 0xFFFFFFFFll) return (int)hipErrorInvalidValue;
         total = (uint32_t)host_chunks;   // the device count above is the same number
-        const int e = all ? 0 : launch_single(in, in_off, in_len, n, out, out_off, out_cap, out_len, status, P, stream);
+        const int e = all ? 0 : launch_single(b, P, stream);
         if (e) return e;
     } else {
     // a pinned word of the stream (the caller holds its launch lock), so the
     // copy is asynchronous and the event covers it
-    uint32_t* h_total = (uint32_t*)bpmd_internal_pinned(stream, 64, 0);
+    uint32_t* h_total = (uint32_t*)bpmd::pinned_block(stream, 64, bpmd::PIN_DEFLATE_CHUNKS);
     if (!h_total) return (int)hipErrorOutOfMemory;
     hipEvent_t ev = nullptr;
     if ((he = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) return (int)he;
@@ -1764,7 +1759,7 @@ int deflate_impl(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_l
         (void)hipEventDestroy(ev);
         return (int)he;
     }
-    int e = all ? 0 : launch_single(in, in_off, in_len, n, out, out_off, out_cap, out_len, status, P, stream);
+    int e = all ? 0 : launch_single(b, P, stream);
     he = hipEventSynchronize(ev);
     (void)hipEventDestroy(ev);
     if (e) return e;
@@ -1795,7 +1790,7 @@ int deflate_impl(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_l
                  o_bits = up(o_items + 4ull * total),
                  o_slots = up(o_bits + 4ull * total),
                  o_cub = up(o_slots + (size_t)SLOT * total), bytes = up(o_cub + cub_bytes);
-    uint8_t* ws = (uint8_t*)bpmd_internal_scratch(stream, bytes, 2);
+    uint8_t* ws = bpmd::scratch_block(stream, bytes, bpmd::SCR_DEFLATE_WS);
     if (!ws) return (int)hipErrorOutOfMemory;
     uint32_t* first = (uint32_t*)(ws + o_first);
     uint32_t* items = (uint32_t*)(ws + o_items);
@@ -1809,8 +1804,7 @@ int deflate_impl(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_l
         const unsigned fgrid = n < 256 * 1024 ? (n + 255) / 256 : 1024;
         hipLaunchKernelGGL(fill_items_kernel, dim3(fgrid), dim3(256), 0, stream, in_len, n, all, first, items);
     }
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    const int cus = bpmd::cu_count();
     P.chain = chain(false);
     // the chunk kernel with the level's history (lz::chunk_hist: 2 KiB, or 4 KiB
     // at the slow levels)
@@ -1818,7 +1812,7 @@ int deflate_impl(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_l
         constexpr int H = decltype(hist_tag)::value;
         const unsigned per_cu = (160u * 1024u) / (unsigned)sizeof(DefLds<H>);
         const unsigned grid = total < (uint32_t)cus * per_cu ? total : (unsigned)cus * per_cu;
-        hipLaunchKernelGGL(deflate_chunks_kernel<H>, dim3(grid), dim3(64), 0, stream, in, in_off, in_len, items,
+        hipLaunchKernelGGL(deflate_chunks_kernel<H>, dim3(grid), dim3(64), 0, stream, b.in, b.in_off, b.in_len, items,
                            first, d_total, slots, bits, d_total + 32, P);
         return 0;
     };
@@ -1838,55 +1832,25 @@ int deflate_impl(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_l
 }
 }  // namespace
 
-extern "C" int bpmd_internal_deflate_bits(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,
-                                          uint32_t n, uint8_t* out, const uint64_t* out_off, const uint32_t* out_cap,
-                                          uint32_t* out_len, int32_t* status, uint32_t* out_bits, int level,
-                                          int window_bits, int strategy, const int* tune, hipStream_t stream)
-{
-    return deflate_impl(in, in_off, in_len, n, out, out_off, out_cap, out_len, status, out_bits, nullptr, nullptr,
-                        level, window_bits, strategy, stream, tune);
-}
-
 // the per-stream deflater's flush (pmd_stream.hip): exact bit lengths, and
 // the stream's earlier plaintext before the message as history (context
 // takeover), hist_len null for none
-extern "C" int bpmd_internal_deflate_bits_hist(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,
-                                               uint32_t n, uint8_t* out, const uint64_t* out_off,
-                                               const uint32_t* out_cap, uint32_t* out_len, int32_t* status,
-                                               uint32_t* out_bits, const uint32_t* hist_len, int level,
-                                               int window_bits, int strategy, const int* tune, hipStream_t stream,
-                                               int64_t host_chunks)
+int bpmd::deflate_bits_hist(const Batch& b, uint32_t* out_bits, const uint32_t* hist_len, int level, int window_bits,
+                            int strategy, const int* tune, hipStream_t stream, int64_t host_chunks)
 {
-    return deflate_impl(in, in_off, in_len, n, out, out_off, out_cap, out_len, status, out_bits, nullptr, hist_len,
-                        level, window_bits, strategy, stream, tune, host_chunks);
+    return deflate_impl(b, out_bits, nullptr, hist_len, level, window_bits, strategy, stream, tune, host_chunks);
 }
 
-extern "C" int bpmd_internal_deflate_keyed(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,
-                                           uint32_t n, uint8_t* out, const uint64_t* out_off, const uint32_t* out_cap,
-                                           uint32_t* out_len, int32_t* status, int level, int window_bits,
-                                           int strategy, const uint32_t* mask_key, hipStream_t stream)
+int bpmd::deflate_keyed(const Batch& b, int level, int window_bits, int strategy, const uint32_t* mask_key,
+                        hipStream_t stream)
 {
-    return deflate_impl(in, in_off, in_len, n, out, out_off, out_cap, out_len, status, nullptr, mask_key, nullptr,
-                        level, window_bits, strategy, stream);
+    return deflate_impl(b, nullptr, mask_key, nullptr, level, window_bits, strategy, stream);
 }
 
-extern "C" int bpmd_internal_deflate_takeover(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,
-                                              uint32_t n, uint8_t* out, const uint64_t* out_off,
-                                              const uint32_t* out_cap, uint32_t* out_len, int32_t* status, int level,
-                                              int window_bits, int strategy, const uint32_t* hist_len,
-                                              hipStream_t stream)
+int bpmd::deflate_takeover(const Batch& b, int level, int window_bits, int strategy, const uint32_t* hist_len,
+                           hipStream_t stream)
 {
-    return deflate_impl(in, in_off, in_len, n, out, out_off, out_cap, out_len, status, nullptr, nullptr, hist_len,
-                        level, window_bits, strategy, stream);
-}
-
-extern "C" int bpmd_internal_deflate(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint32_t n,
-                                     uint8_t* out, const uint64_t* out_off, const uint32_t* out_cap,
-                                     uint32_t* out_len, int32_t* status, int level, int window_bits, int strategy,
-                                     hipStream_t stream)
-{
-    return bpmd_internal_deflate_bits(in, in_off, in_len, n, out, out_off, out_cap, out_len, status, nullptr, level,
-                                      window_bits, strategy, nullptr, stream);
+    return deflate_impl(b, nullptr, nullptr, hist_len, level, window_bits, strategy, stream);
 }
 
 extern "C" int bpmd_diag_deflate_counters(unsigned long long* out, int reset)

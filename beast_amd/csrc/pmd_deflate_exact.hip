@@ -1045,18 +1045,16 @@ deflate_exact_kernel(const uint8_t* __restrict__ in, const uint64_t* __restrict_
 }  // namespace dx
 }  // namespace bpmd
 
-extern "C" void* bpmd_internal_scratch(hipStream_t s, size_t bytes, int which);
-extern "C" const uint32_t* bpmd_internal_lane_order(const uint32_t* in_len, uint32_t n, hipStream_t stream,
-                                                    const uint32_t** keys_out);
+// (here, not at the top: tests/model/exact_host.py compiles the text above the
+// kernel for the host without HIP)
+#include "pmd_internal.h"
 
 // cfg already validated (pmd_capi.hip deflate_impl)
-extern "C" int bpmd_internal_deflate_exact(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,
-                                           uint32_t n, uint8_t* out, const uint64_t* out_off,
-                                           const uint32_t* out_cap, uint32_t* out_len, int32_t* status, int level,
-                                           int window_bits, int mem_level, int strategy, const uint32_t* mask_key,
-                                           hipStream_t stream)
+int bpmd::deflate_exact(const Batch& b, int level, int window_bits, int mem_level, int strategy,
+                        const uint32_t* mask_key, hipStream_t stream)
 {
     using namespace bpmd::dx;
+    const auto& [in, in_off, in_len, n, out, out_off, out_cap, out_len, status] = b;
     if (n == 0) return 0;
     Cfg c;
     c.level = level;
@@ -1064,8 +1062,7 @@ extern "C" int bpmd_internal_deflate_exact(const uint8_t* in, const uint64_t* in
     c.wbits = (uint32_t)window_bits;
     c.hbits = (uint32_t)mem_level + 7;
     c.lit_bufsize = 1u << (mem_level + 6);
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    const int cus = cu_count();
     hipError_t e;
     const size_t trees = (sizeof(Trees) + 15) & ~(size_t)15;
     if (c.hbits <= 12) {
@@ -1083,18 +1080,15 @@ extern "C" int bpmd_internal_deflate_exact(const uint8_t* in, const uint64_t* in
     // waves are latency-bound on it, so as many as the registers allow
     // (BPMD_EXACT_T2_OCC per SIMD; round 3 ran four per CU), taking the
     // messages longest first from a queue (BPMD_EXACT_WAVES_PER_CU overrides)
-    static const unsigned wpc = [] {
-        const char* ev = getenv("BPMD_EXACT_WAVES_PER_CU");
-        const unsigned v = ev ? (unsigned)strtoul(ev, nullptr, 10) : 0u;
-        return v ? v : 4u * BPMD_EXACT_T2_OCC;
-    }();
+    static const unsigned wpc_env = env_uint("BPMD_EXACT_WAVES_PER_CU", 0u),
+                          wpc = wpc_env ? wpc_env : 4u * BPMD_EXACT_T2_OCC;
     const size_t wsz = (size_t)1 << c.wbits;
     const size_t per = ((2 * wsz + MAXM + 64 + 15) & ~(size_t)15) + 2 * wsz + 2 * ((size_t)1 << c.hbits) +
                        3 * (size_t)c.lit_bufsize + 64;
     const unsigned grid = (unsigned)cus * wpc;
-    uint8_t* ws = (uint8_t*)bpmd_internal_scratch(stream, per * grid, 4);
-    uint32_t* qctr = (uint32_t*)bpmd_internal_scratch(stream, 256, 3);
-    const uint32_t* order = bpmd_internal_lane_order(in_len, n, stream, nullptr);
+    uint8_t* ws = scratch_block(stream, per * grid, SCR_EXACT_WS);
+    uint32_t* qctr = (uint32_t*)scratch_block(stream, 256, SCR_EXACT_QUEUE);
+    const uint32_t* order = lane_order(in_len, n, stream, nullptr);
     if (!ws || !qctr) return (int)hipErrorOutOfMemory;
     if (!order || hipMemsetAsync(qctr, 0, sizeof(uint32_t), stream) != hipSuccess) return (int)hipErrorUnknown;
     const size_t t2_lds = trees + (((size_t)1 << c.hbits) <= T2_LDS_HEAD ? 2 * ((size_t)1 << c.hbits) : 0);

@@ -26,6 +26,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "pmd_internal.h"
+
 namespace bpmd {
 namespace frame {
 
@@ -298,15 +300,13 @@ frame_kernel(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_off
 namespace {
 unsigned frame_grid(uint32_t n)
 {
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    const unsigned want = (n + bpmd::frame::WPB - 1) / bpmd::frame::WPB, cap = (unsigned)cus * 8u;
+    const unsigned want = (n + bpmd::frame::WPB - 1) / bpmd::frame::WPB, cap = (unsigned)bpmd::cu_count() * 8u;
     return want < cap ? want : cap;
 }
 }  // namespace
 
-extern "C" int bpmd_internal_mask(uint8_t* data, const uint64_t* off, const uint32_t* len, uint32_t n,
-                                  const uint32_t* key, const uint8_t* phase, hipStream_t stream)
+int bpmd::launch_mask(uint8_t* data, const uint64_t* off, const uint32_t* len, uint32_t n, const uint32_t* key,
+                      const uint8_t* phase, hipStream_t stream)
 {
     if (n == 0) return 0;
     hipLaunchKernelGGL(bpmd::frame::mask_kernel, dim3(frame_grid(n)), dim3(bpmd::frame::WAVE * bpmd::frame::WPB), 0,
@@ -314,8 +314,8 @@ extern "C" int bpmd_internal_mask(uint8_t* data, const uint64_t* off, const uint
     return (int)hipGetLastError();
 }
 
-extern "C" int bpmd_internal_utf8(const uint8_t* data, const uint64_t* off, const uint32_t* len, uint32_t n,
-                                  int32_t* result, const uint8_t* text, int32_t fail_status, hipStream_t stream)
+int bpmd::launch_utf8(const uint8_t* data, const uint64_t* off, const uint32_t* len, uint32_t n, int32_t* result,
+                      const uint8_t* text, int32_t fail_status, hipStream_t stream)
 {
     if (n == 0) return 0;
     hipLaunchKernelGGL(bpmd::frame::utf8_kernel, dim3(frame_grid(n)), dim3(bpmd::frame::WAVE * bpmd::frame::WPB), 0,
@@ -323,8 +323,8 @@ extern "C" int bpmd_internal_utf8(const uint8_t* data, const uint64_t* off, cons
     return (int)hipGetLastError();
 }
 
-extern "C" int bpmd_internal_slide(uint8_t* buf, const uint64_t* base, const uint32_t* pos, const uint32_t* keep,
-                                   uint32_t n, hipStream_t stream)
+int bpmd::launch_slide(uint8_t* buf, const uint64_t* base, const uint32_t* pos, const uint32_t* keep, uint32_t n,
+                       hipStream_t stream)
 {
     if (n == 0) return 0;
     hipLaunchKernelGGL(bpmd::frame::slide_kernel, dim3(frame_grid(n)), dim3(bpmd::frame::WAVE * bpmd::frame::WPB), 0,
@@ -332,10 +332,9 @@ extern "C" int bpmd_internal_slide(uint8_t* buf, const uint64_t* base, const uin
     return (int)hipGetLastError();
 }
 
-extern "C" int bpmd_internal_frame(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, const uint8_t* op,
-                                   const uint8_t* flags, const uint32_t* keys, const uint32_t* key_base,
-                                   uint32_t frame_max, uint32_t n, uint8_t* wire, const uint64_t* wire_off,
-                                   hipStream_t stream)
+int bpmd::launch_frame(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, const uint8_t* op,
+                       const uint8_t* flags, const uint32_t* keys, const uint32_t* key_base, uint32_t frame_max,
+                       uint32_t n, uint8_t* wire, const uint64_t* wire_off, hipStream_t stream)
 {
     if (n == 0) return 0;
     hipLaunchKernelGGL(bpmd::frame::frame_kernel, dim3(frame_grid(n)), dim3(bpmd::frame::WAVE * bpmd::frame::WPB), 0,

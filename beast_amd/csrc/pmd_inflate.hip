@@ -38,6 +38,7 @@
 #include "huff_table.h"
 #include "huff_wave.h"
 #include "wave_util.h"
+#include "pmd_internal.h"
 
 namespace bpmd {
 
@@ -1083,79 +1084,49 @@ inflate_kernel(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_o
 
 // ---------------------------------------------------------------- launcher
 
-extern "C" unsigned bpmd_diag_grid_override;   // pmd_capi.hip; 0 = size the grid by occupancy
-extern "C" void* bpmd_internal_scratch(hipStream_t s, size_t bytes, int which);
 #ifndef BPMD_WAVE_QUEUE
 #define BPMD_WAVE_QUEUE 1
 #endif
 
-extern "C" int bpmd_internal_inflate_keyed_split(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,
-                                           uint32_t n, uint8_t* out, const uint64_t* out_off, const uint32_t* out_cap,
-                                           uint32_t* out_len, int32_t* status, uint32_t raw, const uint32_t* mask_key,
-                                           uint32_t min_in, hipStream_t stream)
+// As many waves as the LDS holds (grid_override != 0: that many), each
+// taking its messages grid-strided or, with more messages than waves (or
+// always_queue), from a work queue.
+static int launch_wave(const bpmd::Batch& b, uint32_t raw, const uint32_t* mask_key, uint32_t min_in,
+                       const uint32_t* order, const uint32_t* limit, unsigned grid_override, bool always_queue,
+                       hipStream_t stream)
 {
     using namespace bpmd;
-    if (n == 0) return 0;
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    if (b.n == 0) return 0;
     const size_t lds = sizeof(WaveLds);
     const unsigned per_cu = (unsigned)(160 * 1024 / lds);
-    unsigned grid = (unsigned)cus * (per_cu ? per_cu : 1);
-    if (bpmd_diag_grid_override) grid = bpmd_diag_grid_override;
-    if (grid > n) grid = n;
-    // more messages than resident waves: a work queue (scratch block 6)
+    unsigned grid = (unsigned)cu_count() * (per_cu ? per_cu : 1);
+    if (grid_override) grid = grid_override;
+    if (grid > b.n) grid = b.n;
     uint32_t* qctr = nullptr;
-    if (BPMD_WAVE_QUEUE && n > grid) {
-        qctr = (uint32_t*)bpmd_internal_scratch(stream, 256, 6);
+    if (always_queue || (BPMD_WAVE_QUEUE && b.n > grid)) {
+        qctr = (uint32_t*)scratch_block(stream, 256, SCR_WAVE_QUEUE);
         if (!qctr || hipMemsetAsync(qctr, 0, sizeof(uint32_t), stream) != hipSuccess) return (int)hipErrorOutOfMemory;
     }
-    hipLaunchKernelGGL(inflate_kernel, dim3(grid), dim3(WAVE), lds, stream, in, in_off, in_len, n, out, out_off,
-                       out_cap, out_len, status, raw, mask_key, min_in, qctr, (const uint32_t*)nullptr,
-                       (const uint32_t*)nullptr);
+    hipLaunchKernelGGL(inflate_kernel, dim3(grid), dim3(WAVE), lds, stream, b.in, b.in_off, b.in_len, b.n, b.out,
+                       b.out_off, b.out_cap, b.out_len, b.status, raw, mask_key, min_in, qctr, order, limit);
     return (int)hipGetLastError();
+}
+
+int bpmd::inflate_keyed_split(const Batch& b, uint32_t raw, const uint32_t* mask_key, uint32_t min_in,
+                              hipStream_t stream)
+{
+    return launch_wave(b, raw, mask_key, min_in, nullptr, nullptr, bpmd_diag_grid_override, false, stream);
 }
 
 // The long payloads of a lane-kernel batch: messages order[0, *limit) (a
 // device count, known only on the device), one wave each from the work queue.
-extern "C" int bpmd_internal_inflate_wave_ordered(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,
-                                                  uint32_t n, uint8_t* out, const uint64_t* out_off,
-                                                  const uint32_t* out_cap, uint32_t* out_len, int32_t* status,
-                                                  uint32_t raw, const uint32_t* mask_key, const uint32_t* order,
-                                                  const uint32_t* limit, hipStream_t stream)
+int bpmd::inflate_wave_ordered(const Batch& b, uint32_t raw, const uint32_t* mask_key, const uint32_t* order,
+                               const uint32_t* limit, hipStream_t stream)
 {
-    using namespace bpmd;
-    if (n == 0) return 0;
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    const size_t lds = sizeof(WaveLds);
-    const unsigned per_cu = (unsigned)(160 * 1024 / lds);
-    unsigned grid = (unsigned)cus * (per_cu ? per_cu : 1);
-    if (grid > n) grid = n;
-    uint32_t* qctr = (uint32_t*)bpmd_internal_scratch(stream, 256, 6);
-    if (!qctr || hipMemsetAsync(qctr, 0, sizeof(uint32_t), stream) != hipSuccess) return (int)hipErrorOutOfMemory;
-    hipLaunchKernelGGL(inflate_kernel, dim3(grid), dim3(WAVE), lds, stream, in, in_off, in_len, n, out, out_off,
-                       out_cap, out_len, status, raw, mask_key, 0u, qctr, order, limit);
-    return (int)hipGetLastError();
+    return launch_wave(b, raw, mask_key, 0u, order, limit, 0u, true, stream);
 }
 
-extern "C" int bpmd_internal_inflate_keyed(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,
-                                           uint32_t n, uint8_t* out, const uint64_t* out_off, const uint32_t* out_cap,
-                                           uint32_t* out_len, int32_t* status, uint32_t raw, const uint32_t* mask_key,
-                                           hipStream_t stream)
-{
-    return bpmd_internal_inflate_keyed_split(in, in_off, in_len, n, out, out_off, out_cap, out_len, status, raw,
-                                             mask_key, 0u, stream);
-}
-
-extern "C" int bpmd_internal_inflate(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint32_t n,
-                                     uint8_t* out, const uint64_t* out_off, const uint32_t* out_cap,
-                                     uint32_t* out_len, int32_t* status, uint32_t raw, hipStream_t stream)
-{
-    return bpmd_internal_inflate_keyed(in, in_off, in_len, n, out, out_off, out_cap, out_len, status, raw, nullptr,
-                                       stream);
-}
-
-extern "C" int bpmd_internal_init_fixed(void)
+int bpmd::init_fixed()
 {
     using namespace bpmd;
     uint8_t lens[288];

@@ -52,17 +52,7 @@
 #include "bp.h"
 #include "canon.h"
 #include "pmd_common.h"
-
-extern "C" void* bpmd_internal_scratch(hipStream_t s, size_t bytes, int which);
-extern "C" int bpmd_internal_inflate_lane3_seg(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,
-                                               uint32_t n_tasks, const void* tasks, uint16_t* sym, void* res,
-                                               uint32_t raw, uint32_t* qctr, uint32_t grid_wgs, hipStream_t stream,
-                                               const uint32_t* n_dev);
-extern "C" int bpmd_internal_inflate_wave_ordered(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,
-                                                  uint32_t n, uint8_t* out, const uint64_t* out_off,
-                                                  const uint32_t* out_cap, uint32_t* out_len, int32_t* status,
-                                                  uint32_t raw, const uint32_t* mask_key, const uint32_t* order,
-                                                  const uint32_t* limit, hipStream_t stream);
+#include "pmd_internal.h"
 
 namespace bpmd {
 namespace bp {
@@ -1674,7 +1664,7 @@ std::atomic<int> g_bp_skim{-1};  // the skim: -1 from BPMD_BP_SKIM, 0 off, 1 on
 uint8_t* dw_alloc(hipStream_t s, size_t bytes)
 {
     if (g_bp_fail.load() > 0 && g_bp_fail.fetch_sub(1) > 0) return nullptr;
-    return (uint8_t*)bpmd_internal_scratch(s, bytes, 11);
+    return bpmd::scratch_block(s, bytes, bpmd::SCR_BP_DECODE);
 }
 
 // the entry of (device, stream), created zeroed; nullptr when the pinned
@@ -1747,7 +1737,7 @@ void grow_to(BpCaps* c, unsigned long long t, unsigned long long w)
 }  // namespace
 
 // frees the pinned totals and event of a stream about to be destroyed
-extern "C" void bpmd_internal_bp_release(hipStream_t s)
+void bpmd::bp_release(hipStream_t s)
 {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return;
@@ -1768,8 +1758,8 @@ extern "C" void bpmd_internal_bp_release(hipStream_t s)
 // msgs payloads -- bp_stats_kernel's bounds: regions of >= R_MIN bytes, at
 // most one more per payload; slot words 2 (len + regions) x 1.25 x
 // min(cap / len, 4) + SLACK per region + the guard per payload.
-extern "C" int bpmd_internal_bp_reserve(hipStream_t s, unsigned long long in_bytes, unsigned long long out_bytes,
-                                        unsigned long long msgs)
+int bpmd::bp_reserve(hipStream_t s, unsigned long long in_bytes, unsigned long long out_bytes,
+                     unsigned long long msgs)
 {
     using namespace bpmd::bp;
     int dev = 0;
@@ -1785,15 +1775,14 @@ extern "C" int bpmd_internal_bp_reserve(hipStream_t s, unsigned long long in_byt
     return 0;
 }
 
-extern "C" int bpmd_internal_inflate_bp(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint32_t n,
-                                        uint8_t* out, const uint64_t* out_off, const uint32_t* out_cap,
-                                        uint32_t* out_len, int32_t* status, uint32_t raw, const uint32_t* order,
-                                        const uint32_t* nlong, hipStream_t s)
+int bpmd::inflate_bp(const Batch& b, uint32_t raw, const uint32_t* order, const uint32_t* nlong, hipStream_t s)
 {
     using namespace bpmd::bp;
+    const auto& [in, in_off, in_len, n, out, out_off, out_cap, out_len, status] = b;
     if (n == 0) return 0;
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    const int cus = cu_count();
     // this stream's capacity, grown to what an earlier call needed
     unsigned long long cap_tasks = 0, cap_words = 0;
     Totals* seen = nullptr;
@@ -1814,7 +1803,7 @@ extern "C" int bpmd_internal_inflate_bp(const uint8_t* in, const uint64_t* in_of
         seen = c->seen;
         ev = c->ev;
     }
-    // per-payload workspace (scratch block 10): stats, regions, words, their
+    // per-payload workspace (SCR_BP_STATS): stats, regions, words, their
     // exclusive sums, totals, fit, queues, scan temp
     size_t tmp1 = 0, tmp2 = 0;
     if (hipcub::DeviceScan::ExclusiveSum(nullptr, tmp1, (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)n, s) !=
@@ -1828,7 +1817,7 @@ extern "C" int bpmd_internal_inflate_bp(const uint8_t* in, const uint64_t* in_of
                  sz = al256(o_tmp + (tmp1 > tmp2 ? tmp1 : tmp2));
     // q: [0] scan queue, [1] resolve queue, [2] fallback count, [3] seg queue,
     // [4-5] long bytes, [6] payloads that fit, [7] their tasks
-    uint8_t* ws = (uint8_t*)bpmd_internal_scratch(s, sz, 10);
+    uint8_t* ws = scratch_block(s, sz, SCR_BP_STATS);
     if (!ws) return (int)hipErrorOutOfMemory;
     Stat* st = (Stat*)(ws + o_st);
     uint32_t* reg = (uint32_t*)(ws + o_reg);
@@ -1844,11 +1833,8 @@ extern "C" int bpmd_internal_inflate_bp(const uint8_t* in, const uint64_t* in_of
     hipLaunchKernelGGL(bp_sum_kernel, dim3(n / 256 + 1 < 1024 ? n / 256 + 1 : 1024), dim3(256), 0, s, in_len, order,
                        nlong, n, total);
     // BPMD_BP_SEGS (diagnostics): target segments per lane of the chip
-    static const uint32_t segs = [] {
-        const char* e = getenv("BPMD_BP_SEGS");
-        const uint32_t v = e ? (uint32_t)strtoul(e, nullptr, 10) : 0u;
-        return v ? v : 4u;   // 2 / 4 / 8: C4 8-way shard 10.3 / 9.1 / 9.3 ms, C5 92 / 96 / 100 GiB/s
-    }();
+    // (0: the default 4.  2 / 4 / 8: C4 8-way shard 10.3 / 9.1 / 9.3 ms, C5 92 / 96 / 100 GiB/s)
+    static const uint32_t segs_env = env_uint("BPMD_BP_SEGS", 0u), segs = segs_env ? segs_env : 4u;
     hipLaunchKernelGGL(bp_stats_kernel, dim3((n + 255) / 256), dim3(256), 0, s, in_len, out_cap, order, nlong, n, total,
                        256u * (uint32_t)cus, segs, st, reg, words);
     if (hipGetLastError() != hipSuccess) return (int)hipErrorUnknown;
@@ -1871,7 +1857,7 @@ extern "C" int bpmd_internal_inflate_bp(const uint8_t* in, const uint64_t* in_of
         cap_tasks = c->tasks;
         cap_words = c->words;
     }
-    // decode workspace (scratch block 11), sized by the capacity: tasks,
+    // decode workspace (SCR_BP_DECODE), sized by the capacity: tasks,
     // results, fallback list, region map, marks, symbols.  A block that
     // cannot be had: the capacity it replaces, else none.
     uint8_t* dw = dw_alloc(s, dw_bytes(cap_tasks, cap_words, n));
@@ -1939,11 +1925,8 @@ extern "C" int bpmd_internal_inflate_bp(const uint8_t* in, const uint64_t* in_of
     // BPMD_BP_DYN_STRIDE: pass 2 searches every n-th pending region (default
     // 1; 4 measured C4 8-way Beast shard 16.6 -> 17.8 ms, C5 17.6 -> 15.7 ms,
     // profiles/r05j_ab_compact_canon.log)
-    static const uint32_t dyn_stride = [] {
-        const char* e = getenv("BPMD_BP_DYN_STRIDE");
-        const uint32_t v = e ? (uint32_t)strtoul(e, nullptr, 10) : 0u;
-        return v ? v : 1u;   // 1: the per-payload stride (bp_scan_kernel)
-    }();
+    // (0 or 1: the per-payload stride, bp_scan_kernel)
+    static const uint32_t stride_env = env_uint("BPMD_BP_DYN_STRIDE", 0u), dyn_stride = stride_env ? stride_env : 1u;
     hipLaunchKernelGGL(bp_scan_kernel<false>, dim3(scan_wgs), dim3(64 * SCAN_WAVES), 0, s, in, in_off, in_len, order,
                        rmap, fit + 1, st, tbase, tasks, marked, dyn_stride);
     // the skim (payloads without sync markers), then pass 2 on the regions no
@@ -1965,8 +1948,7 @@ extern "C" int bpmd_internal_inflate_bp(const uint8_t* in, const uint64_t* in_of
     if (hipGetLastError() != hipSuccess) return (int)hipErrorUnknown;
     // segments: a work queue over the device-side task count
     const uint32_t wgs = 4u * cus;
-    int e = bpmd_internal_inflate_lane3_seg(in, in_off, in_len, (uint32_t)cap_tasks, tasks, sym, res, raw, q + 3, wgs,
-                                            s, fit + 1);
+    int e = inflate_lane3_seg(in, in_off, in_len, (uint32_t)cap_tasks, tasks, sym, res, raw, q + 3, wgs, s, fit + 1);
     if (e) return e;
     // resolve: the serial walk per payload (default), or the segment-parallel
     // form (BPMD_BP_RESOLVE=parallel; measured slower: a reference in
@@ -1991,8 +1973,7 @@ extern "C" int bpmd_internal_inflate_bp(const uint8_t* in, const uint64_t* in_of
     }
     // payloads over the capacity or whose output outgrew the slots: the wave
     // kernel, from the list
-    return bpmd_internal_inflate_wave_ordered(in, in_off, in_len, n, out, out_off, out_cap, out_len, status, raw,
-                                              nullptr, fb, q + 2, s);
+    return inflate_wave_ordered(b, raw, nullptr, fb, q + 2, s);
 }
 
 // the fixed-block skim on (1) or off (0) for the following calls (tests, A/B)

@@ -44,6 +44,7 @@
 #include "canon.h"
 #include "bp.h"
 #include "lane_io.h"
+#include "pmd_internal.h"
 
 namespace bpmd {
 namespace lp3 {
@@ -1687,37 +1688,36 @@ inflate_lane3_seg_kernel(const uint8_t* __restrict__ in, const uint64_t* __restr
 }  // namespace lp3
 }  // namespace bpmd
 
-extern "C" int bpmd_internal_inflate_lane3_seg(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,
-                                               uint32_t n_tasks, const void* tasks, uint16_t* sym, void* res,
-                                               uint32_t raw, uint32_t* qctr, uint32_t grid_wgs, hipStream_t stream,
-                                               const uint32_t* n_dev)
+// one lane per item, 64 to a workgroup; from a work queue at most grid_wgs workgroups
+static unsigned lane_grid(uint32_t n, const uint32_t* qctr, uint32_t grid_wgs)
+{
+    const unsigned grid = (n + bpmd::lp3::WG_MSGS - 1) / bpmd::lp3::WG_MSGS;
+    return qctr && grid_wgs && grid > grid_wgs ? grid_wgs : grid;
+}
+
+int bpmd::inflate_lane3_seg(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint32_t n_tasks,
+                            const bp::SegTask* tasks, uint16_t* sym, bp::SegRes* res, uint32_t raw, uint32_t* qctr,
+                            uint32_t grid_wgs, hipStream_t stream, const uint32_t* n_dev)
 {
     using namespace bpmd::lp3;
     if (n_tasks == 0) return 0;
-    unsigned grid = (n_tasks + WG_MSGS - 1) / WG_MSGS;
-    if (qctr && grid_wgs && grid > grid_wgs) grid = grid_wgs;
-    hipLaunchKernelGGL(inflate_lane3_seg_kernel, dim3(grid), dim3(128), WG_MSGS * STRIDE, stream, in, in_off, in_len,
-                       n_tasks, (const bpmd::bp::SegTask*)tasks, sym, (bpmd::bp::SegRes*)res, raw, qctr, n_dev);
+    hipLaunchKernelGGL(inflate_lane3_seg_kernel, dim3(lane_grid(n_tasks, qctr, grid_wgs)), dim3(128), WG_MSGS * STRIDE,
+                       stream, in, in_off, in_len, n_tasks, tasks, sym, res, raw, qctr, n_dev);
     return (int)hipGetLastError();
 }
 
 // order: NULL or the order messages are taken in (e.g. longest first);
 // qctr: NULL (one message per lane) or a zeroed device counter: then the grid
 // is at most grid_wgs workgroups and lanes take further messages from it.
-extern "C" int bpmd_internal_inflate_lane3(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint32_t n,
-                                           uint8_t* out, const uint64_t* out_off, const uint32_t* out_cap,
-                                           uint32_t* out_len, int32_t* status, uint32_t raw, const uint32_t* mask_key,
-                                           const uint32_t* hist_len, uint32_t hist_max, uint32_t max_in,
-                                           const uint32_t* order, uint32_t* qctr, uint32_t grid_wgs,
-                                           const uint32_t* skip, hipStream_t stream)
+int bpmd::inflate_lane3(const Batch& b, uint32_t raw, const uint32_t* mask_key, const uint32_t* hist_len,
+                        uint32_t hist_max, uint32_t max_in, const uint32_t* order, uint32_t* qctr, uint32_t grid_wgs,
+                        const uint32_t* skip, hipStream_t stream)
 {
     using namespace bpmd::lp3;
-    if (n == 0) return 0;
-    unsigned grid = (n + WG_MSGS - 1) / WG_MSGS;
-    if (qctr && grid_wgs && grid > grid_wgs) grid = grid_wgs;
-    hipLaunchKernelGGL(inflate_lane3_kernel, dim3(grid), dim3(128), WG_MSGS * STRIDE, stream, in, in_off, in_len, n,
-                       out, out_off, out_cap, out_len, status, raw, mask_key, hist_len, hist_max, max_in, order, qctr,
-                       skip);
+    if (b.n == 0) return 0;
+    hipLaunchKernelGGL(inflate_lane3_kernel, dim3(lane_grid(b.n, qctr, grid_wgs)), dim3(128), WG_MSGS * STRIDE, stream,
+                       b.in, b.in_off, b.in_len, b.n, b.out, b.out_off, b.out_cap, b.out_len, b.status, raw, mask_key,
+                       hist_len, hist_max, max_in, order, qctr, skip);
     return (int)hipGetLastError();
 }
 
@@ -1741,12 +1741,9 @@ __global__ void __launch_bounds__(256) order_keys_kernel(const uint32_t* __restr
 }  // namespace lp3
 }  // namespace bpmd
 
-extern "C" void* bpmd_internal_scratch(hipStream_t s, size_t bytes, int which);
-
 // order[0, n) = message indices, longest payload first; returns null on error.
 // keys_out (optional): the sorted keys (in_len >> 6, descending).
-extern "C" const uint32_t* bpmd_internal_lane_order(const uint32_t* in_len, uint32_t n, hipStream_t stream,
-                                                    const uint32_t** keys_out)
+const uint32_t* bpmd::lane_order(const uint32_t* in_len, uint32_t n, hipStream_t stream, const uint32_t** keys_out)
 {
     size_t temp = 0;
     if (hipcub::DeviceRadixSort::SortPairsDescending(nullptr, temp, (const uint32_t*)nullptr, (uint32_t*)nullptr,
@@ -1754,7 +1751,7 @@ extern "C" const uint32_t* bpmd_internal_lane_order(const uint32_t* in_len, uint
                                                      stream) != hipSuccess)
         return nullptr;
     const size_t words = (size_t)n * 4;   // key in, key out, index in, index out
-    uint8_t* p = (uint8_t*)bpmd_internal_scratch(stream, words * 4 + temp + 256, 5);
+    uint8_t* p = bpmd::scratch_block(stream, words * 4 + temp + 256, bpmd::SCR_ORDER);
     if (!p) return nullptr;
     uint32_t* kin = (uint32_t*)p;
     uint32_t* kout = kin + n;
@@ -1780,7 +1777,7 @@ extern "C" const uint32_t* bpmd_internal_lane_order(const uint32_t* in_len, uint
 // compressed length above share_pct % of the batch's compressed bytes per
 // resident lane (block-parallel: 125 % by default, BPMD_LONG_SHARE_PCT, so
 // the work queue ends near the per-lane share; wave kernel: 200 %; the
-// values live in pmd_capi.hip inflate_impl), and never below min_thr.  The count is computed on the device from the sorted keys, so the
+// values live in inflate_plan.h), and never below min_thr.  The count is computed on the device from the sorted keys, so the
 // call stays asynchronous: split[0] = total compressed bytes (u64),
 // split[2] = number of long payloads = a prefix of the longest-first order.
 namespace bpmd {
@@ -1819,13 +1816,13 @@ __global__ void long_count_kernel(const uint32_t* __restrict__ keys, uint32_t n,
 }  // namespace bpmd
 
 // returns a device pointer to the number of long payloads (a prefix of the
-// order bpmd_internal_lane_order returned with `keys`), or null on error.
+// order bpmd::lane_order returned with `keys`), or null on error.
 // lanes == 0: a fixed threshold of min_thr compressed bytes (0: every payload).
 extern "C" const uint32_t* bpmd_internal_lane_long_split(const uint32_t* in_len, const uint32_t* keys, uint32_t n,
                                                          uint32_t lanes, uint32_t min_thr, uint32_t share_pct,
                                                          hipStream_t stream)
 {
-    unsigned long long* split = (unsigned long long*)bpmd_internal_scratch(stream, 256, 9);
+    unsigned long long* split = (unsigned long long*)bpmd::scratch_block(stream, 256, bpmd::SCR_LONG_SPLIT);
     if (!split || hipMemsetAsync(split, 0, 16, stream) != hipSuccess) return nullptr;
     const uint32_t blocks = n / 256 + 1 < 1024 ? n / 256 + 1 : 1024;
     hipLaunchKernelGGL(bpmd::lp3::sum_in_kernel, dim3(blocks), dim3(256), 0, stream, in_len, n, split);

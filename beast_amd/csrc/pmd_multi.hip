@@ -20,8 +20,7 @@
 #include <vector>
 
 #include "../../include/beast_pmd.h"
-
-extern "C" void* bpmd_internal_scratch(hipStream_t s, size_t bytes, int which);
+#include "pmd_internal.h"
 
 namespace {
 
@@ -37,10 +36,8 @@ __global__ void sum_lens_kernel(const uint32_t* __restrict__ len, uint32_t n, un
 typedef int (*batch_fn)(const bpmd_cfg*, const uint8_t*, const uint64_t*, const uint32_t*, uint32_t, uint8_t*,
                         const uint64_t*, const uint32_t*, uint32_t*, int32_t*, void*);
 
-extern "C" void* bpmd_internal_stream_mutex(hipStream_t s);
-
 // one shard: its batch call, then (out_bytes) the per-shard total on the
-// shard's own stream, after its batch (scratch block 8), under the stream's
+// shard's own stream, after its batch, under the stream's
 // launch lock like every scratch user
 int run_shard(batch_fn fn, const bpmd_cfg* cfg, const bpmd_shard& s, bool want_total, unsigned long long** sum)
 {
@@ -49,10 +46,10 @@ int run_shard(batch_fn fn, const bpmd_cfg* cfg, const bpmd_shard& s, bool want_t
                s.d_status, s.stream);
     if (r || !want_total) return r;
     const hipStream_t hs = (hipStream_t)s.stream;
-    std::mutex* mu = (std::mutex*)bpmd_internal_stream_mutex(hs);
+    std::mutex* mu = bpmd::stream_mutex(hs);
     if (!mu) return BPMD_R_HIP_ERROR;
     std::lock_guard<std::mutex> launch(*mu);
-    *sum = (unsigned long long*)bpmd_internal_scratch(hs, 256, 8);
+    *sum = (unsigned long long*)bpmd::scratch_block(hs, 256, bpmd::SCR_MULTI_TOTALS);
     if (!*sum || hipMemsetAsync(*sum, 0, sizeof(unsigned long long), hs) != hipSuccess) return BPMD_R_HIP_ERROR;
     if (s.n_msgs) {
         const uint32_t blocks = s.n_msgs / 256 + 1 < 1024 ? s.n_msgs / 256 + 1 : 1024;

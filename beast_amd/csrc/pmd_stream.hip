@@ -35,18 +35,8 @@
 
 #include "../../include/beast_pmd.h"
 #include "lz_core.h"
+#include "pmd_internal.h"
 #include "zstream.h"
-
-extern "C" int bpmd_internal_zstream_write(void* st, const uint8_t* in, uint64_t n_in, uint8_t* out, uint64_t cap,
-                                           int flush, void* res, hipStream_t stream);
-extern "C" void bpmd_internal_scratch_release(hipStream_t stream);
-extern "C" int bpmd_internal_deflate_bits_hist(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,
-                                               uint32_t n, uint8_t* out, const uint64_t* out_off,
-                                               const uint32_t* out_cap, uint32_t* out_len, int32_t* status,
-                                               uint32_t* out_bits, const uint32_t* hist_len, int level,
-                                               int window_bits, int strategy, const int* tune, hipStream_t stream,
-                                               int64_t host_chunks);
-extern "C" int bpmd_internal_zstream_write_batch(const void* calls, uint32_t n, hipStream_t stream);
 
 struct bpmd_stream {
     bool is_deflate = true;
@@ -167,10 +157,10 @@ int run_one(bpmd_stream* s, const uint8_t* in, size_t n, size_t out_cap, std::ve
     // chunks of the chunk-parallel path: every chunk with a history window,
     // else only messages over one chunk (pmd_deflate.hip chunk_count)
     const int64_t chunks = hn ? (int64_t)((n + 4095) / 4096) : (n > 4096 ? (int64_t)((n + 4095) / 4096) : 0);
-    const int e = bpmd_internal_deflate_bits_hist(d + in_at, &dm->in_off, &dm->in_len, 1, d + out_at, &dm->out_off,
-                                                  &dm->out_cap, &dm->out_len, &dm->status, &dm->bits,
-                                                  hn ? &dm->hist_len : nullptr, s->level, s->wbits, s->strategy,
-                                                  s->tuned ? s->tune4 : nullptr, s->hs, chunks);
+    const bpmd::Batch b{d + in_at, &dm->in_off, &dm->in_len, 1, d + out_at, &dm->out_off, &dm->out_cap, &dm->out_len,
+                        &dm->status};
+    const int e = bpmd::deflate_bits_hist(b, &dm->bits, hn ? &dm->hist_len : nullptr, s->level, s->wbits, s->strategy,
+                                          s->tuned ? s->tune4 : nullptr, s->hs, chunks);
     if (e) return fail();
     if (hipMemcpyAsync(h, d, out_at + out_cap, hipMemcpyDeviceToHost, s->hs) != hipSuccess) return fail();
     if (hipStreamSynchronize(s->hs) != hipSuccess) return BPMD_R_HIP_ERROR;
@@ -809,15 +799,14 @@ void deflate_group(Arena& A, std::vector<Job*>& jobs)
     }
     uint8_t* d = A.d;
     const bool whole = in_at <= (4u << 20);
+    const bpmd::Batch b{d + in_at, (const uint64_t*)(d + m_in_off), (const uint32_t*)(d + m_in_len), k, d + out_at,
+                        (const uint64_t*)(d + m_out_off), (const uint32_t*)(d + m_out_cap), (uint32_t*)(d + m_out_len),
+                        (int32_t*)(d + m_status)};
     bool ok = hipMemcpyAsync(d, h, out_at, hipMemcpyHostToDevice, A.hs) == hipSuccess &&
               (ib == 0 || hipMemcpyAsync(d + in_at, h + in_at, ib, hipMemcpyHostToDevice, A.hs) == hipSuccess) &&
-              bpmd_internal_deflate_bits_hist(d + in_at, (const uint64_t*)(d + m_in_off),
-                                              (const uint32_t*)(d + m_in_len), k, d + out_at,
-                                              (const uint64_t*)(d + m_out_off), (const uint32_t*)(d + m_out_cap),
-                                              (uint32_t*)(d + m_out_len), (int32_t*)(d + m_status),
-                                              (uint32_t*)(d + m_bits), hist ? (const uint32_t*)(d + m_hist) : nullptr,
-                                              s0->level, s0->wbits, s0->strategy, s0->tuned ? s0->tune4 : nullptr,
-                                              A.hs, chunks) == 0 &&
+              bpmd::deflate_bits_hist(b, (uint32_t*)(d + m_bits), hist ? (const uint32_t*)(d + m_hist) : nullptr,
+                                      s0->level, s0->wbits, s0->strategy, s0->tuned ? s0->tune4 : nullptr, A.hs,
+                                      chunks) == 0 &&
               hipMemcpyAsync(h, d, whole ? in_at : out_at, hipMemcpyDeviceToHost, A.hs) == hipSuccess &&
               hipStreamSynchronize(A.hs) == hipSuccess;
     if (!ok) return fail_all(jobs, A.hs);

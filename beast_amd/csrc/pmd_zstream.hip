@@ -36,6 +36,7 @@
 #include "huff_table.h"
 #include "huff_wave.h"
 #include "wave_util.h"
+#include "pmd_internal.h"
 #include <atomic>
 #include <cstdlib>
 #endif
@@ -1373,17 +1374,23 @@ extern "C" int bpmd_diag_set_zstream_parallel(int on)
     return 0;
 }
 
+// the setting, or the environment's (read once): BPMD_ZSTREAM_PAR any number
+// but 0, BPMD_ZSTREAM_HPAR on unless set to 0
+static int zstream_par()
+{
+    static const int env_par = [] {
+        const char* e = getenv("BPMD_ZSTREAM_PAR");
+        return (e ? (atoi(e) ? 1 : 0) : 1) | (bpmd::env_on("BPMD_ZSTREAM_HPAR") ? 0 : 8);
+    }();
+    const int o = g_zst_par.load();
+    return o < 0 ? env_par : o;
+}
+
 extern "C" int bpmd_internal_zstream_write(void* st, const uint8_t* in, uint64_t n_in, uint8_t* out, uint64_t cap,
                                            int flush, void* res, hipStream_t stream)
 {
     using namespace bpmd::zst;
-    static const int env_par = [] {
-        const char* e = getenv("BPMD_ZSTREAM_PAR");
-        const char* hp = getenv("BPMD_ZSTREAM_HPAR");
-        return (e ? (atoi(e) ? 1 : 0) : 1) | (hp && hp[0] == '0' ? 8 : 0);
-    }();
-    const int o = g_zst_par.load();
-    int par = o < 0 ? env_par : o;
+    int par = zstream_par();
 #ifdef BPMD_PROF
     static const int env_warm = [] {
         const char* e = getenv("BPMD_ZSTREAM_WARM");
@@ -1402,13 +1409,7 @@ extern "C" int bpmd_internal_zstream_write_batch(const void* calls, uint32_t n, 
 {
     using namespace bpmd::zst;
     if (n == 0) return 0;
-    static const int env_par = [] {
-        const char* e = getenv("BPMD_ZSTREAM_PAR");
-        const char* hp = getenv("BPMD_ZSTREAM_HPAR");
-        return (e ? (atoi(e) ? 1 : 0) : 1) | (hp && hp[0] == '0' ? 8 : 0);
-    }();
-    const int o = g_zst_par.load();
-    const int par = o < 0 ? env_par : o;
+    const int par = zstream_par();
     hipLaunchKernelGGL(zstream_write_batch_kernel, dim3(n), dim3(bpmd::WAVE), 0, stream, (const ZCall*)calls, par);
     return (int)hipGetLastError();
 }
