@@ -8,8 +8,9 @@
 //   returned by the kernel) and appends the flush's own bits the way the
 //   reference's doWrite does (deflate_stream.ipp:357-499): Flush::block
 //   leaves the last partial byte pending, partial adds tr_align's empty
-//   static block, sync/full add the empty stored block 000 + pad +
-//   00 00 FF FF, finish adds a final empty block and reports end_of_stream.
+//   static block, sync/full/trees add the empty stored block 000 + pad +
+//   00 00 FF FF (full also drops the history, as clear_hash() does), finish
+//   adds a final empty block and reports end_of_stream.
 //   Pending output, duplicate-flush need_buffers, stream_error and
 //   invalid_argument follow doWrite.
 // inflate: the reference's decoder state lives on the device (zstream.h) and
@@ -63,7 +64,7 @@ struct bpmd_stream {
     unsigned nbits = 0;
     int last_flush = -1;        // boost::none
     bool finished = false;      // finish_state
-    bool inited = false;        // inited_ (deflate_stream.hpp:252): set by the first write after a reset
+    bool inited = false;        // inited_ (deflate_stream.hpp:252): set by the first write or prime after a reset
     bool tuned = false;         // tune() values in force (until reset / a level change)
     int tune4[4] = {0, 0, 0, 0};
     // device scratch
@@ -216,6 +217,15 @@ void align_bits(bpmd_stream* s)
     if (s->nbits) put_bits(s, 0, 8 - s->nbits);
 }
 
+// tr_stored_block(nullptr, 0): 000, pad to a byte, 00 00 FF FF
+void put_empty_stored(bpmd_stream* s)
+{
+    put_bits(s, 0, 3);
+    align_bits(s);
+    put_bits(s, 0x0000, 16);
+    put_bits(s, 0xFFFF, 16);
+}
+
 void drain(bpmd_stream* s, bpmd_zparams* zs)
 {
     const size_t avail = s->pend.size() - s->pend_pos;
@@ -247,6 +257,16 @@ void reset_deflate(bpmd_stream* s)
     s->finished = false;
     s->inited = false;   // the next write's init() -> lm_init() restores the level's table row
     s->tuned = false;
+}
+
+// maybe_init() -> init() (deflate_stream.hpp:593, deflate_stream.ipp:597-691): the first write() or
+// prime() after a reset; init() leaves last_flush_ = Flush::none (:685), so
+// a first write(Flush::none) without input is need_buffers
+void init_deflate(bpmd_stream* s)
+{
+    if (s->inited) return;
+    s->inited = true;
+    s->last_flush = BPMD_FLUSH_NONE;
 }
 
 // one flush's compression: through the micro-batcher when it is on (below)
@@ -290,7 +310,7 @@ extern "C" int bpmd_deflate_stream_write(bpmd_stream* s, bpmd_zparams* zs, int f
     if (!zs->next_in && zs->avail_in) return BPMD_R_INVALID_ARGUMENT;   // throws invalid_argument
     if (!zs->next_out || (s->finished && flush != BPMD_FLUSH_FINISH)) return BPMD_STREAM_ERROR;
     if (zs->avail_out == 0) return BPMD_NEED_BUFFERS;
-    s->inited = true;   // maybe_init() (deflate_stream.ipp:361)
+    init_deflate(s);   // maybe_init() (deflate_stream.ipp:361)
     const int old = s->last_flush;
     s->last_flush = flush;
     if (has_pending(s)) {
@@ -319,6 +339,12 @@ extern "C" int bpmd_deflate_stream_write(bpmd_stream* s, bpmd_zparams* zs, int f
             int r = run_flush(s, cap, out, st, nb);
             if (r) return r;
             if (st != BPMD_OK) return BPMD_STREAM_ERROR;
+            // The kernels' blocks start at bit 0 of their output, and the
+            // stored blocks and chunk markers among them are padded to a byte
+            // from there.  After Flush::block, Flush::partial or a prime() the
+            // stream is inside a byte: an empty stored block (what Flush::sync
+            // emits) brings it to a byte boundary first.
+            if (s->nbits) put_empty_stored(s);
             put_bitstring(s, out.data(), nb);
             add_history(s, s->in.data(), s->in.size());
             s->in.clear();
@@ -329,11 +355,12 @@ extern "C" int bpmd_deflate_stream_write(bpmd_stream* s, bpmd_zparams* zs, int f
             put_bits(s, 0, 7);
             break;
         case BPMD_FLUSH_SYNC:
-        case BPMD_FLUSH_FULL:        // tr_stored_block(nullptr, 0): 000, pad, 00 00 FF FF
-            put_bits(s, 0, 3);
-            align_bits(s);
-            put_bits(s, 0x0000, 16);
-            put_bits(s, 0xFFFF, 16);
+        case BPMD_FLUSH_FULL:
+        case BPMD_FLUSH_TREES:       // `flush != Flush::block` (deflate_stream.ipp:467-470):
+            put_empty_stored(s);
+            // clear_hash() (deflate_stream.ipp:474-483): nothing after a full
+            // flush refers to anything before it
+            if (flush == BPMD_FLUSH_FULL) s->hist.clear();
             break;
         case BPMD_FLUSH_FINISH:      // last block: empty fixed block with BFINAL = 1
             put_bits(s, 1u | (1u << 1), 3);
@@ -341,7 +368,7 @@ extern "C" int bpmd_deflate_stream_write(bpmd_stream* s, bpmd_zparams* zs, int f
             align_bits(s);
             s->finished = true;
             break;
-        default:                     // block / trees: the block is complete, bits stay pending
+        default:                     // block: the block is complete, bits stay pending
             break;
         }
         drain(s, zs);
@@ -360,15 +387,23 @@ extern "C" int bpmd_deflate_stream_params(bpmd_stream* s, bpmd_zparams* zs, int 
     if (level < 0 || level > 9 || strategy < BPMD_STRATEGY_NORMAL || strategy > BPMD_STRATEGY_FIXED)
         return BPMD_STREAM_ERROR;
     int r = BPMD_OK;
-    if (!s->in.empty() && (level != s->level || strategy != s->strategy)) {
+    // doParams calls doWrite(Flush::block) when the strategy or the level's
+    // parser changes after any input (deflate_stream.ipp:334-341), buffered
+    // input or not: the call is also what the next write's duplicate-flush
+    // test sees as the previous flush.  Here a flush compresses all it has
+    // buffered with one level, so any change of level flushes as well.
+    const bool new_parser = lz::level_params(level).parser != lz::level_params(s->level).parser;
+    const bool ref_flush = (strategy != s->strategy || new_parser) && zs->total_in != 0;
+    if (ref_flush || (!s->in.empty() && level != s->level)) {
         r = bpmd_deflate_stream_write(s, zs, BPMD_FLUSH_BLOCK);
-        if (r == BPMD_NEED_BUFFERS) r = BPMD_OK;
+        if (r == BPMD_NEED_BUFFERS && !has_pending(s)) r = BPMD_OK;   // `&& pending_ == 0` (:339)
     }
-    if (r == BPMD_OK) {
-        if (level != s->level) s->tuned = false;   // doParams reloads the level's table row
-        s->level = level;
-        s->strategy = strategy;
-    }
+    // the new values hold whatever doWrite returned (deflate_stream.ipp:342-350); with no
+    // room for output the input stays buffered and is compressed with them, as Beast's
+    // unparsed lookahead is
+    if (level != s->level) s->tuned = false;   // doParams reloads the level's table row
+    s->level = level;
+    s->strategy = strategy;
     return r;
 }
 
@@ -402,6 +437,7 @@ extern "C" int bpmd_deflate_stream_prime(bpmd_stream* s, int bits, int value)
     // deflate_stream::prime (deflate_stream.ipp:340-355): insert up to 16 bits
     if (!s || !s->is_deflate) return BPMD_R_INVALID_ARGUMENT;
     if (bits < 0 || bits > 16) return BPMD_NEED_BUFFERS;
+    init_deflate(s);   // maybe_init() (deflate_stream.ipp:560): a tune() after prime() is kept
     if (bits) put_bits(s, (uint32_t)value & ((1u << bits) - 1u), (unsigned)bits);
     return BPMD_OK;
 }
@@ -899,6 +935,14 @@ extern "C" int bpmd_stream_batching(int max_calls, int max_delay_us)
     (void)batch_max();   // the environment's defaults read first, then replaced
     g_bdelay.store(max_delay_us);
     g_bmax.store(max_calls);
+    return BPMD_R_OK;
+}
+
+extern "C" int bpmd_stream_batching_get(int* max_calls, int* max_delay_us)
+{
+    const int m = batch_max();   // the environment's defaults, unless replaced
+    if (max_calls) *max_calls = m;
+    if (max_delay_us) *max_delay_us = g_bdelay.load();
     return BPMD_R_OK;
 }
 

@@ -408,7 +408,8 @@ int bpmd_deflate_stream_create(int level, int window_bits, int mem_level, int st
 /* deflate_stream::reset() (deflate_stream.hpp:123-127) */
 int bpmd_deflate_stream_reset(bpmd_stream* s);
 /* deflate_stream::write(zs, flush, ec) (deflate_stream.ipp:357-499): returns
- * the zlib::error value (0 = none) or BPMD_R_INVALID_ARGUMENT where it throws */
+ * the zlib::error value (0 = none) or BPMD_R_INVALID_ARGUMENT where it throws.
+ * What each Flush value emits and which guarantees hold: DESIGN.md 8. */
 int bpmd_deflate_stream_write(bpmd_stream* s, bpmd_zparams* zs, int flush);
 /* deflate_stream::params(zs, level, strategy, ec) (deflate_stream.ipp:307-338) */
 int bpmd_deflate_stream_params(bpmd_stream* s, bpmd_zparams* zs, int level, int strategy);
@@ -416,7 +417,7 @@ int bpmd_deflate_stream_params(bpmd_stream* s, bpmd_zparams* zs, int level, int 
  * (deflate_stream.hpp:163-181, deflate_stream.ipp:307-317): replaces the
  * level's good/lazy/nice/chain limits for the following writes (the GPU
  * parser still caps the chain walk); like the reference, a
- * tune before the stream's first write is undone by its lazy init. */
+ * tune before the stream's first write or prime is undone by its lazy init. */
 int bpmd_deflate_stream_tune(bpmd_stream* s, int good_length, int max_lazy, int nice_length, int max_chain);
 /* deflate_stream::pending(value, bits) (deflate_stream.hpp:344-348) */
 int bpmd_deflate_stream_pending(bpmd_stream* s, unsigned* value, int* bits);
@@ -455,6 +456,8 @@ void bpmd_stream_destroy(bpmd_stream* s);
  * off.  Default: 256 calls, no delay (environment: BPMD_STREAM_BATCH,
  * BPMD_STREAM_BATCH_DELAY_US). */
 int bpmd_stream_batching(int max_calls, int max_delay_us);
+/* The setting in force (either pointer may be NULL), e.g. to put it back. */
+int bpmd_stream_batching_get(int* max_calls, int* max_delay_us);
 /* out[0] inflate write() calls through the batcher, out[1] their launches,
  * out[2] deflate flushes, out[3] their deflater calls; reset != 0 zeroes them. */
 int bpmd_stream_batch_stats(unsigned long long* out, int reset);

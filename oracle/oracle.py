@@ -57,6 +57,11 @@ def lib():
         L.bzo_deflate_write.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
         L.bzo_deflate_upper_bound.argtypes = [ctypes.c_void_p, ctypes.c_size_t]
         L.bzo_deflate_upper_bound.restype = ctypes.c_size_t
+        L.bzo_deflate_tune.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 4
+        L.bzo_deflate_tune.restype = None
+        L.bzo_deflate_params.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
+        L.bzo_deflate_pending.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(ctypes.c_int)]
+        L.bzo_deflate_prime.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
         L.bzo_deflate_upper_bound_free.argtypes = [ctypes.c_size_t]
         L.bzo_deflate_upper_bound_free.restype = ctypes.c_size_t
         L.bzo_pmd_deflate_msg.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
@@ -264,6 +269,28 @@ class Deflater:
 
     def write(self, zs: ZParams, flush: str) -> int:
         return self.L.bzo_deflate_write(self.z, ctypes.byref(zs), FLUSH[flush])
+
+    def params(self, zs: ZParams, level: int, strategy: int) -> int:
+        """deflate_stream::params (deflate_stream.ipp:319-351)."""
+        return self.L.bzo_deflate_params(self.z, ctypes.byref(zs), level, strategy)
+
+    def tune(self, good_length: int, max_lazy: int, nice_length: int, max_chain: int):
+        """deflate_stream::tune (deflate_stream.ipp:305-317)."""
+        self.L.bzo_deflate_tune(self.z, good_length, max_lazy, nice_length, max_chain)
+
+    def pending(self):
+        """deflate_stream::pending (deflate_stream.ipp:582-590): (bytes, bits)."""
+        v, b = ctypes.c_uint(0), ctypes.c_int(0)
+        self.L.bzo_deflate_pending(self.z, ctypes.byref(v), ctypes.byref(b))
+        return v.value, b.value
+
+    def prime(self, bits: int, value: int) -> int:
+        """deflate_stream::prime (deflate_stream.ipp:556-580)."""
+        return self.L.bzo_deflate_prime(self.z, bits, value)
+
+    def upper_bound(self, n: int) -> int:
+        """deflate_stream::upper_bound (deflate_stream.ipp:283-303)."""
+        return self.L.bzo_deflate_upper_bound(self.z, n)
 
     def __del__(self):
         try:

@@ -52,18 +52,25 @@ def test_impl_base_codec_uses_compile():
     assert r.returncode == 0, r.stderr
 
 
-def _build_cpu_echo(name="ws_echo"):
-    """ws_echo.cpp (or another harness) linked against
-    tests/cpp/oracle_backend.c (Beast's zlib restated, CPU) instead of
-    libbeast_pmd.so: the same harness, timed the same way, with the
-    reference's CPU codec (test infrastructure)."""
+def _build_oracle_backend():
+    """tests/cpp/oracle_backend.c over liboracle.so: the per-stream C ABI of
+    include/beast_pmd.h on Beast's zlib restated (CPU, test infrastructure).
+    Also what tests/deflate_scripts.py drives beside libbeast_pmd.so."""
     os.makedirs(BUILD, exist_ok=True)
     subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "liboracle.so"], check=True)
     odir = os.path.join(ROOT, "oracle")
     lib = os.path.join(BUILD, "libbpmd_oracle_backend.so")
-    out = os.path.join(BUILD, name + "_cpu")
     subprocess.run(["gcc", "-O2", "-fPIC", "-shared", "-o", lib, os.path.join(CPP, "oracle_backend.c"),
                     "-L", odir, "-loracle", f"-Wl,-rpath,{odir}"], check=True)
+    return lib
+
+
+def _build_cpu_echo(name="ws_echo"):
+    """ws_echo.cpp (or another harness) linked against the oracle backend
+    instead of libbeast_pmd.so: the same harness, timed the same way, with
+    the reference's CPU codec (test infrastructure)."""
+    _build_oracle_backend()
+    out = os.path.join(BUILD, name + "_cpu")
     subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", "-Werror", "-DBPMD_CPU_BACKEND", "-I",
                     os.path.join(ROOT, "include"), os.path.join(CPP, name + ".cpp"), "-o", out, "-L", BUILD,
                     "-lbpmd_oracle_backend", f"-Wl,-rpath,{BUILD}", "-lpthread"], check=True)

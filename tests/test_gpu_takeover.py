@@ -73,25 +73,46 @@ def test_distance_past_the_window_is_invalid():
                 assert st[c] == expect[c][r][0], (r, c, st[c], expect[c][r][0])
 
 
-def test_takeover_deflate_round_trips_and_shrinks():
+def _periodic_messages(rng, c, rounds):
+    """One connection's messages as consecutive pieces of a text of period P
+    (tests/deflate_scripts.py periodic): the cheapest match of every byte
+    past the first period is exactly P back, in an earlier message for a
+    piece shorter than P.  P on both sides of max_dist = 2^wbits - 262 for
+    windowBits 9 (250) and 10 (762) and of the 2048- and 4096-byte chunk
+    histories."""
+    from tests.deflate_scripts import periodic
+    period = (100, 250, 251, 300, 700, 762, 763, 2047, 2048, 2049, 4096, 5000)[c % 12]
+    lens = [rng.choice([1, 300, 2000, 4096, 6000]) for _ in range(rounds)]
+    text = periodic(period, sum(lens), seed=c % 5)
+    cuts = [sum(lens[:r]) for r in range(rounds + 1)]
+    return [text[a:b] for a, b in zip(cuts, cuts[1:])]
+
+
+@pytest.mark.parametrize("level,wbits", [(6, 15), (1, 10), (9, 9), (0, 15)])
+def test_takeover_deflate_round_trips_and_shrinks(level, wbits):
     """GPU deflate with context takeover: every connection's payload stream
-    inflates (oracle, window kept) back to its messages, and reaching into
-    earlier messages makes the payloads smaller than independent ones."""
+    inflates (oracle, window kept, at the deflater's windowBits: a match from
+    beyond the window is invalid_distance) back to its messages, and above
+    level 0 reaching into earlier messages makes the payloads smaller than
+    independent ones."""
     import torch
     from beast_amd import pmd
     rng = random.Random(31)
     n_conn, rounds = 150, 5
     msgs = []
     for c in range(n_conn):
-        msgs.append([bytes(synth.make_batch("json", [rng.choice([1, 300, 2000, 4096, 6000])], seed=c * 7 + r)[0])
-                     for r in range(rounds)])
-    td = pmd.TakeoverDeflater(n_conn, level=6, max_msg=6000)
+        if wbits == 15:
+            msgs.append([bytes(synth.make_batch("json", [rng.choice([1, 300, 2000, 4096, 6000])], seed=c * 7 + r)[0])
+                         for r in range(rounds)])
+        else:
+            msgs.append(_periodic_messages(rng, c, rounds))
+    td = pmd.TakeoverDeflater(n_conn, level=level, window_bits=wbits, max_msg=6000)
     pls = [[None] * rounds for _ in range(n_conn)]
     took = plain = 0
     for r in range(rounds):
         src = pmd.Batch.from_host([msgs[c][r] for c in range(n_conn)])
         res = td.deflate(src)
-        ind = pmd.deflate_batch(src, level=6)
+        ind = pmd.deflate_batch(src, level=level, window_bits=wbits)
         torch.cuda.synchronize()
         assert res.status.cpu().tolist() == [0] * n_conn
         outs = res.out.to_host()
@@ -101,7 +122,10 @@ def test_takeover_deflate_round_trips_and_shrinks():
             took += sum(len(o) for o in outs)
             plain += sum(ind.out.len.cpu().tolist())
     for c in range(n_conn):
-        got = O.pmd_inflate_stream(pls[c], cap=6000)
+        got = O.pmd_inflate_stream(pls[c], cap=6000, wbits=wbits)
         assert [g[0] for g in got] == [0] * rounds, c
         assert [g[1] for g in got] == msgs[c], c
-    assert took < plain, (took, plain)
+    if level > 0:
+        assert took < plain, (took, plain)
+    else:   # stored blocks: every payload holds its message's bytes
+        assert took >= sum(len(m[r]) for m in msgs for r in range(1, rounds)), took
