@@ -1477,7 +1477,10 @@ deflate_kernel(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_o
 constexpr unsigned SLOT = 4736;   // >= bpmd_deflate_upper_bound(CHUNK) + 2, 16-byte multiple
 constexpr int CHUNK_HIST = BPMD_CHUNK_HIST;   // (lz_core.h) history bytes before each chunk (and before a takeover message)
 
-__device__ __forceinline__ uint32_t chunk_count(uint32_t len, bool all)
+// chunks of the chunk-parallel path: every chunk of a message with a history
+// window (all), else only messages over one chunk.  Shared with the host
+// (bpmd::deflate_chunks below: the count the per-stream deflater passes in).
+__host__ __device__ __forceinline__ uint32_t chunk_count(uint32_t len, bool all)
 {
     return (all || len > CHUNK) ? (len + CHUNK - 1) / CHUNK : 0u;
 }
@@ -1831,6 +1834,8 @@ int deflate_impl(const bpmd::Batch& b, uint32_t* out_bits, const uint32_t* mask_
     return (int)hipGetLastError();
 }
 }  // namespace
+
+int64_t bpmd::deflate_chunks(uint32_t n, bool hist) { return dfl::chunk_count(n, hist); }
 
 // the per-stream deflater's flush (pmd_stream.hip): exact bit lengths, and
 // the stream's earlier plaintext before the message as history (context

@@ -105,6 +105,9 @@ int deflate_keyed(const Batch& b, int level, int window_bits, int strategy, cons
                   hipStream_t stream);
 int deflate_takeover(const Batch& b, int level, int window_bits, int strategy, const uint32_t* hist_len,
                      hipStream_t stream);
+// the chunk count of one message of n bytes, with a history window or not:
+// the sum over a batch is deflate_bits_hist's host_chunks
+int64_t deflate_chunks(uint32_t n, bool hist);
 int deflate_bits_hist(const Batch& b, uint32_t* out_bits, const uint32_t* hist_len, int level, int window_bits,
                       int strategy, const int* tune, hipStream_t stream, int64_t host_chunks);
 int deflate_exact(const Batch& b, int level, int window_bits, int mem_level, int strategy, const uint32_t* mask_key,

@@ -3,16 +3,9 @@
 // zlib::deflate_stream / zlib::inflate_stream write() semantics, executed by
 // the GPU kernels.  Host code only.
 //
-// deflate: input is buffered until a flush; each flush compresses the
-//   buffered bytes on the GPU (blocks with BFINAL = 0, exact bit length
-//   returned by the kernel) and appends the flush's own bits the way the
-//   reference's doWrite does (deflate_stream.ipp:357-499): Flush::block
-//   leaves the last partial byte pending, partial adds tr_align's empty
-//   static block, sync/full/trees add the empty stored block 000 + pad +
-//   00 00 FF FF (full also drops the history, as clear_hash() does), finish
-//   adds a final empty block and reports end_of_stream.
-//   Pending output, duplicate-flush need_buffers, stream_error and
-//   invalid_argument follow doWrite.
+// deflate: the call protocol is deflate_writer.h (no HIP in it); here is its
+//   device step, one transport for a flush alone and for a batch of them
+//   (deflate_group), and the C ABI's forwards.
 // inflate: the reference's decoder state lives on the device (zstream.h) and
 //   each write() is one launch of the per-stream kernel (pmd_zstream.hip),
 //   which runs inflate_stream.ipp's state machine with its bit reservoir and
@@ -35,242 +28,78 @@
 #include <vector>
 
 #include "../../include/beast_pmd.h"
-#include "lz_core.h"
+#include "deflate_writer.h"
 #include "pmd_internal.h"
 #include "zstream.h"
 
+namespace {
+
+// a device block, its pinned mirror and the HIP stream they use: a
+// coalescer's leader's, or a deflate stream's own when the batcher is off
+struct Arena {
+    hipStream_t hs = nullptr;
+    uint8_t* d = nullptr;
+    uint8_t* h = nullptr;
+    size_t cap = 0;
+    size_t floor;   // the smallest block allocated
+    explicit Arena(size_t floor_) : floor(floor_) {}
+    bool reserve(size_t need)
+    {
+        if (!hs && hipStreamCreateWithFlags(&hs, hipStreamNonBlocking) != hipSuccess) {
+            hs = nullptr;
+            return false;
+        }
+        if (need <= cap) return true;
+        if (d) (void)hipFree(d);
+        if (h) (void)hipHostFree(h);
+        d = h = nullptr;
+        cap = 0;
+        const size_t c = std::max<size_t>(need + need / 2, floor);
+        if (hipMalloc((void**)&d, c) != hipSuccess) {
+            d = nullptr;
+            return false;
+        }
+        if (hipHostMalloc((void**)&h, c, hipHostMallocDefault) != hipSuccess) {
+            (void)hipFree(d);
+            d = h = nullptr;
+            return false;
+        }
+        cap = c;
+        return true;
+    }
+};
+
+}  // namespace
+
 struct bpmd_stream {
     bool is_deflate = true;
-    // deflate parameters
-    int level = 6, wbits = 15, mem_level = 9, strategy = 0;
-    // inflate: windowBits, device state (zstream.h State + Result), call buffers
-    int inf_wbits = 15;
-    void* zst = nullptr;
-    bool zreset = true;         // a reset() to apply before the next write()
-    uint8_t* din = nullptr;
-    size_t din_cap = 0;
-    uint8_t* dout = nullptr;
-    size_t dout_cap = 0;
-    // deflate: buffered message bytes; the plaintext already compressed since
-    // the last reset (its last BPMD_CHUNK_HIST bytes: the history the next
-    // flush's matches may reach into, as Beast's window does across flushes
-    // and, under context takeover, across messages)
-    std::vector<uint8_t> in;
-    std::vector<uint8_t> hist;
-    // deflate: output not yet handed out, plus < 8 pending bits
-    std::vector<uint8_t> pend;
-    size_t pend_pos = 0;
-    uint32_t bits = 0;
-    unsigned nbits = 0;
-    int last_flush = -1;        // boost::none
-    bool finished = false;      // finish_state
-    bool inited = false;        // inited_ (deflate_stream.hpp:252): set by the first write or prime after a reset
-    bool tuned = false;         // tune() values in force (until reset / a level change)
-    int tune4[4] = {0, 0, 0, 0};
-    // device scratch
-    hipStream_t hs = nullptr;
-    uint8_t* dmem = nullptr;
-    size_t dcap = 0;
-    // pinned host staging for the call's copies (a copy from pageable memory
-    // is staged by the runtime and waits; from pinned memory it is one DMA)
-    uint8_t* hpin = nullptr;
-    size_t hpin_cap = 0;
+    struct Deflate {
+        bpmd::DeflateWriter w;
+        // the batcher off: the stream's own block (64 KiB at least: a server
+        // may hold thousands of these), made by its first flush
+        Arena arena{1 << 16};
+    } def;
+    struct Inflate {
+        // windowBits, device state (zstream.h State + Result), call buffers
+        int wbits = 15;
+        void* zst = nullptr;
+        bool zreset = true;         // a reset() to apply before the next write()
+        uint8_t* din = nullptr;
+        size_t din_cap = 0;
+        uint8_t* dout = nullptr;
+        size_t dout_cap = 0;
+        // the batcher off: the stream's HIP stream and its pinned host staging
+        // for the call's copies (a copy from pageable memory is staged by the
+        // runtime and waits; from pinned memory it is one DMA)
+        hipStream_t hs = nullptr;
+        uint8_t* hpin = nullptr;
+        size_t hpin_cap = 0;
+    } inf;
 };
 
 namespace {
 
-// the stream's pinned staging buffer, at least `need` bytes
-uint8_t* pinned(bpmd_stream* s, size_t need)
-{
-    if (need <= s->hpin_cap) return s->hpin;
-    if (s->hpin) (void)hipHostFree(s->hpin);
-    s->hpin = nullptr;
-    s->hpin_cap = 0;
-    const size_t c = std::max<size_t>(need + need / 2, 1 << 16);
-    if (hipHostMalloc((void**)&s->hpin, c, hipHostMallocDefault) != hipSuccess) {
-        s->hpin = nullptr;
-        return nullptr;
-    }
-    s->hpin_cap = c;
-    return s->hpin;
-}
-
-int ensure_device(bpmd_stream* s, size_t need)
-{
-    if (!s->hs && hipStreamCreateWithFlags(&s->hs, hipStreamNonBlocking) != hipSuccess) return BPMD_R_HIP_ERROR;
-    if (need <= s->dcap) return BPMD_R_OK;
-    if (s->dmem) (void)hipFree(s->dmem);
-    s->dmem = nullptr;
-    s->dcap = 0;
-    size_t cap = std::max<size_t>(need, 1 << 16);
-    if (hipMalloc(&s->dmem, cap) != hipSuccess) return BPMD_R_HIP_ERROR;
-    s->dcap = cap;
-    return BPMD_R_OK;
-}
-
-struct Meta {
-    uint64_t in_off, out_off;
-    uint32_t in_len, out_cap, out_len, bits;
-    int32_t status;
-    uint32_t hist_len;
-    uint32_t pad[5];
-};
-static_assert(sizeof(Meta) == 64, "meta block");
-
-// one flush's bytes through the deflate kernels with the stream's history in
-// front of them; returns 0 or a negative bpmd_result.  Device block:
-// [meta 64 B][output][history + input]; the host stages meta and input in
-// pinned memory, so the call is two H2D copies, the kernels (the chunk count
-// is known here, so the deflater reads nothing back), one D2H of meta and
-// output together and one wait.
-int run_one(bpmd_stream* s, const uint8_t* in, size_t n, size_t out_cap, std::vector<uint8_t>& out, int32_t& status,
-            uint32_t& bits)
-{
-    const size_t hn = s->hist.size();
-    if (n + hn > 0xFFFFFFFFu || out_cap > 0xFFFFFFFFu) return BPMD_R_INVALID_ARGUMENT;
-    int r = bpmd_init();
-    if (r) return r;
-    const size_t out_at = 64, in_at = (out_at + out_cap + 15) & ~size_t(15), total = in_at + hn + n;
-    if ((r = ensure_device(s, total + 16)) != 0) return r;
-    uint8_t* h = pinned(s, total + 16);
-    if (!h) return BPMD_R_HIP_ERROR;
-    Meta m{};
-    m.in_off = hn;
-    m.out_off = 0;
-    m.in_len = (uint32_t)n;
-    m.out_cap = (uint32_t)out_cap;
-    m.hist_len = (uint32_t)hn;
-    std::memcpy(h, &m, sizeof m);
-    if (hn) std::memcpy(h + in_at, s->hist.data(), hn);
-    if (n) std::memcpy(h + in_at + hn, in, n);
-    uint8_t* d = s->dmem;
-    // after the first copy from the pinned buffer is queued, every error
-    // return first waits for the stream: the next call refills (or frees)
-    // that buffer while the DMA could still read it
-    auto fail = [&]() {
-        (void)hipStreamSynchronize(s->hs);
-        return BPMD_R_HIP_ERROR;
-    };
-    if (hipMemcpyAsync(d, h, sizeof m, hipMemcpyHostToDevice, s->hs) != hipSuccess) return fail();
-    if (hn + n && hipMemcpyAsync(d + in_at, h + in_at, hn + n, hipMemcpyHostToDevice, s->hs) != hipSuccess)
-        return fail();
-    Meta* dm = (Meta*)d;
-    // chunks of the chunk-parallel path: every chunk with a history window,
-    // else only messages over one chunk (pmd_deflate.hip chunk_count)
-    const int64_t chunks = hn ? (int64_t)((n + 4095) / 4096) : (n > 4096 ? (int64_t)((n + 4095) / 4096) : 0);
-    const bpmd::Batch b{d + in_at, &dm->in_off, &dm->in_len, 1, d + out_at, &dm->out_off, &dm->out_cap, &dm->out_len,
-                        &dm->status};
-    const int e = bpmd::deflate_bits_hist(b, &dm->bits, hn ? &dm->hist_len : nullptr, s->level, s->wbits, s->strategy,
-                                          s->tuned ? s->tune4 : nullptr, s->hs, chunks);
-    if (e) return fail();
-    if (hipMemcpyAsync(h, d, out_at + out_cap, hipMemcpyDeviceToHost, s->hs) != hipSuccess) return fail();
-    if (hipStreamSynchronize(s->hs) != hipSuccess) return BPMD_R_HIP_ERROR;
-    std::memcpy(&m, h, sizeof m);
-    if (m.out_len > out_cap) return BPMD_R_HIP_ERROR;
-    out.assign(h + out_at, h + out_at + m.out_len);
-    status = m.status;
-    bits = m.bits;
-    return BPMD_R_OK;
-}
-
-// the flushed bytes become history; only the last lz::chunk_hist(level) are
-// used (kept: the most any level uses)
-void add_history(bpmd_stream* s, const uint8_t* p, size_t n)
-{
-    constexpr size_t keep = lz::CHUNK_HIST_DEEP > BPMD_CHUNK_HIST ? lz::CHUNK_HIST_DEEP : BPMD_CHUNK_HIST;
-    if (n >= keep) {
-        s->hist.assign(p + n - keep, p + n);
-        return;
-    }
-    s->hist.insert(s->hist.end(), p, p + n);
-    if (s->hist.size() > keep) s->hist.erase(s->hist.begin(), s->hist.end() - (ptrdiff_t)keep);
-}
-
-// ------------------------------------------------------------ deflate bits
-
-void put_bits(bpmd_stream* s, uint32_t v, unsigned n)
-{
-    s->bits |= v << s->nbits;
-    s->nbits += n;
-    while (s->nbits >= 8) {
-        s->pend.push_back((uint8_t)s->bits);
-        s->bits >>= 8;
-        s->nbits -= 8;
-    }
-}
-
-// append `nb` bits of the little-endian bit string p
-void put_bitstring(bpmd_stream* s, const uint8_t* p, uint64_t nb)
-{
-    uint64_t i = 0;
-    if (s->nbits == 0) {
-        const size_t whole = (size_t)(nb >> 3);
-        s->pend.insert(s->pend.end(), p, p + whole);
-        i = (uint64_t)whole * 8;
-    }
-    for (; i + 8 <= nb; i += 8) put_bits(s, p[i >> 3], 8);
-    if (i < nb) put_bits(s, p[i >> 3] & ((1u << (nb - i)) - 1), (unsigned)(nb - i));
-}
-
-void align_bits(bpmd_stream* s)
-{
-    if (s->nbits) put_bits(s, 0, 8 - s->nbits);
-}
-
-// tr_stored_block(nullptr, 0): 000, pad to a byte, 00 00 FF FF
-void put_empty_stored(bpmd_stream* s)
-{
-    put_bits(s, 0, 3);
-    align_bits(s);
-    put_bits(s, 0x0000, 16);
-    put_bits(s, 0xFFFF, 16);
-}
-
-void drain(bpmd_stream* s, bpmd_zparams* zs)
-{
-    const size_t avail = s->pend.size() - s->pend_pos;
-    const size_t k = std::min(avail, zs->avail_out);
-    if (k) {
-        std::memcpy(zs->next_out, s->pend.data() + s->pend_pos, k);
-        zs->next_out = (uint8_t*)zs->next_out + k;
-        zs->avail_out -= k;
-        zs->total_out += k;
-        s->pend_pos += k;
-    }
-    if (s->pend_pos == s->pend.size()) {
-        s->pend.clear();
-        s->pend_pos = 0;
-    }
-}
-
-bool has_pending(const bpmd_stream* s) { return s->pend_pos < s->pend.size(); }
-
-void reset_deflate(bpmd_stream* s)
-{
-    s->in.clear();
-    s->hist.clear();
-    s->pend.clear();
-    s->pend_pos = 0;
-    s->bits = 0;
-    s->nbits = 0;
-    s->last_flush = -1;
-    s->finished = false;
-    s->inited = false;   // the next write's init() -> lm_init() restores the level's table row
-    s->tuned = false;
-}
-
-// maybe_init() -> init() (deflate_stream.hpp:593, deflate_stream.ipp:597-691): the first write() or
-// prime() after a reset; init() leaves last_flush_ = Flush::none (:685), so
-// a first write(Flush::none) without input is need_buffers
-void init_deflate(bpmd_stream* s)
-{
-    if (s->inited) return;
-    s->inited = true;
-    s->last_flush = BPMD_FLUSH_NONE;
-}
-
-// one flush's compression: through the micro-batcher when it is on (below)
-int run_flush(bpmd_stream* s, size_t out_cap, std::vector<uint8_t>& out, int32_t& status, uint32_t& bits);
+int run_flush(void* stream, bpmd::DeflateStep& st);
 
 }  // namespace
 
@@ -279,167 +108,48 @@ extern "C" int bpmd_deflate_stream_create(int level, int window_bits, int mem_le
 {
     if (!out) return BPMD_R_INVALID_ARGUMENT;
     *out = nullptr;
-    // deflate_stream.ipp:235-253
-    if (level == -1) level = 6;
-    if (window_bits == 8) window_bits = 9;
-    if (level < 0 || level > 9 || window_bits < 8 || window_bits > 15 || mem_level < 1 || mem_level > 9 ||
-        strategy < BPMD_STRATEGY_NORMAL || strategy > BPMD_STRATEGY_FIXED)
-        return BPMD_R_INVALID_ARGUMENT;
     bpmd_stream* s = new (std::nothrow) bpmd_stream();
     if (!s) return BPMD_R_INVALID_ARGUMENT;
-    s->is_deflate = true;
-    s->level = level;
-    s->wbits = window_bits;
-    s->mem_level = mem_level;
-    s->strategy = strategy;
+    const int r = s->def.w.create(level, window_bits, mem_level, strategy);
+    if (r) {
+        delete s;
+        return r;
+    }
+    s->def.w.compress = run_flush;
+    s->def.w.ctx = s;
     *out = s;
     return BPMD_R_OK;
 }
 
 extern "C" int bpmd_deflate_stream_reset(bpmd_stream* s)
 {
-    if (!s || !s->is_deflate) return BPMD_R_INVALID_ARGUMENT;
-    reset_deflate(s);
-    return BPMD_R_OK;
+    return (!s || !s->is_deflate) ? BPMD_R_INVALID_ARGUMENT : s->def.w.reset();
 }
 
 extern "C" int bpmd_deflate_stream_write(bpmd_stream* s, bpmd_zparams* zs, int flush)
 {
-    if (!s || !s->is_deflate || !zs || flush < BPMD_FLUSH_NONE || flush > BPMD_FLUSH_TREES)
-        return BPMD_R_INVALID_ARGUMENT;
-    if (!zs->next_in && zs->avail_in) return BPMD_R_INVALID_ARGUMENT;   // throws invalid_argument
-    if (!zs->next_out || (s->finished && flush != BPMD_FLUSH_FINISH)) return BPMD_STREAM_ERROR;
-    if (zs->avail_out == 0) return BPMD_NEED_BUFFERS;
-    init_deflate(s);   // maybe_init() (deflate_stream.ipp:361)
-    const int old = s->last_flush;
-    s->last_flush = flush;
-    if (has_pending(s)) {
-        drain(s, zs);
-        if (zs->avail_out == 0) {
-            s->last_flush = -1;
-            return BPMD_OK;
-        }
-    } else if (zs->avail_in == 0 && old >= 0 && flush <= old && flush != BPMD_FLUSH_FINISH) {
-        return BPMD_NEED_BUFFERS;
-    }
-    if (s->finished && zs->avail_in) return BPMD_NEED_BUFFERS;
-    if (zs->avail_in) {
-        const uint8_t* p = (const uint8_t*)zs->next_in;
-        s->in.insert(s->in.end(), p, p + zs->avail_in);
-        zs->next_in = p + zs->avail_in;
-        zs->total_in += zs->avail_in;
-        zs->avail_in = 0;
-    }
-    if (flush != BPMD_FLUSH_NONE && !s->finished) {
-        if (!s->in.empty()) {
-            std::vector<uint8_t> out;
-            int32_t st = 0;
-            uint32_t nb = 0;
-            const size_t cap = bpmd_deflate_upper_bound(s->in.size()) + 16;
-            int r = run_flush(s, cap, out, st, nb);
-            if (r) return r;
-            if (st != BPMD_OK) return BPMD_STREAM_ERROR;
-            // The kernels' blocks start at bit 0 of their output, and the
-            // stored blocks and chunk markers among them are padded to a byte
-            // from there.  After Flush::block, Flush::partial or a prime() the
-            // stream is inside a byte: an empty stored block (what Flush::sync
-            // emits) brings it to a byte boundary first.
-            if (s->nbits) put_empty_stored(s);
-            put_bitstring(s, out.data(), nb);
-            add_history(s, s->in.data(), s->in.size());
-            s->in.clear();
-        }
-        switch (flush) {
-        case BPMD_FLUSH_PARTIAL:     // tr_align: empty static block
-            put_bits(s, 1u << 1, 3);
-            put_bits(s, 0, 7);
-            break;
-        case BPMD_FLUSH_SYNC:
-        case BPMD_FLUSH_FULL:
-        case BPMD_FLUSH_TREES:       // `flush != Flush::block` (deflate_stream.ipp:467-470):
-            put_empty_stored(s);
-            // clear_hash() (deflate_stream.ipp:474-483): nothing after a full
-            // flush refers to anything before it
-            if (flush == BPMD_FLUSH_FULL) s->hist.clear();
-            break;
-        case BPMD_FLUSH_FINISH:      // last block: empty fixed block with BFINAL = 1
-            put_bits(s, 1u | (1u << 1), 3);
-            put_bits(s, 0, 7);
-            align_bits(s);
-            s->finished = true;
-            break;
-        default:                     // block: the block is complete, bits stay pending
-            break;
-        }
-        drain(s, zs);
-        if (zs->avail_out == 0) s->last_flush = -1;
-    }
-    if (flush == BPMD_FLUSH_FINISH) return has_pending(s) ? BPMD_OK : BPMD_END_OF_STREAM;
-    return BPMD_OK;
+    return (!s || !s->is_deflate || !zs) ? BPMD_R_INVALID_ARGUMENT : s->def.w.write(zs, flush);
 }
 
 extern "C" int bpmd_deflate_stream_params(bpmd_stream* s, bpmd_zparams* zs, int level, int strategy)
 {
-    // deflate_stream::params (deflate_stream.ipp:307-338): buffered input is
-    // compressed with the old parameters first, as a Flush::block
-    if (!s || !s->is_deflate || !zs) return BPMD_R_INVALID_ARGUMENT;
-    if (level == -1) level = 6;
-    if (level < 0 || level > 9 || strategy < BPMD_STRATEGY_NORMAL || strategy > BPMD_STRATEGY_FIXED)
-        return BPMD_STREAM_ERROR;
-    int r = BPMD_OK;
-    // doParams calls doWrite(Flush::block) when the strategy or the level's
-    // parser changes after any input (deflate_stream.ipp:334-341), buffered
-    // input or not: the call is also what the next write's duplicate-flush
-    // test sees as the previous flush.  Here a flush compresses all it has
-    // buffered with one level, so any change of level flushes as well.
-    const bool new_parser = lz::level_params(level).parser != lz::level_params(s->level).parser;
-    const bool ref_flush = (strategy != s->strategy || new_parser) && zs->total_in != 0;
-    if (ref_flush || (!s->in.empty() && level != s->level)) {
-        r = bpmd_deflate_stream_write(s, zs, BPMD_FLUSH_BLOCK);
-        if (r == BPMD_NEED_BUFFERS && !has_pending(s)) r = BPMD_OK;   // `&& pending_ == 0` (:339)
-    }
-    // the new values hold whatever doWrite returned (deflate_stream.ipp:342-350); with no
-    // room for output the input stays buffered and is compressed with them, as Beast's
-    // unparsed lookahead is
-    if (level != s->level) s->tuned = false;   // doParams reloads the level's table row
-    s->level = level;
-    s->strategy = strategy;
-    return r;
+    return (!s || !s->is_deflate || !zs) ? BPMD_R_INVALID_ARGUMENT : s->def.w.params(zs, level, strategy);
 }
 
 extern "C" int bpmd_deflate_stream_tune(bpmd_stream* s, int good_length, int max_lazy, int nice_length, int max_chain)
 {
-    // deflate_stream::tune (deflate_stream.hpp:163-181, deflate_stream.ipp:307-317).
-    // Before the stream's first write the values are overwritten by the lazy
-    // init()'s lm_init() (deflate_stream.ipp:688, 697-710), so they only take
-    // effect on an initialised stream, until the next reset.
-    if (!s || !s->is_deflate) return BPMD_R_INVALID_ARGUMENT;
-    if (!s->inited) return BPMD_R_OK;
-    s->tune4[0] = good_length;
-    s->tune4[1] = max_lazy;
-    s->tune4[2] = nice_length;
-    s->tune4[3] = max_chain;
-    s->tuned = true;
-    return BPMD_R_OK;
+    return (!s || !s->is_deflate) ? BPMD_R_INVALID_ARGUMENT
+                                  : s->def.w.tune(good_length, max_lazy, nice_length, max_chain);
 }
 
 extern "C" int bpmd_deflate_stream_pending(bpmd_stream* s, unsigned* value, int* bits)
 {
-    // deflate_stream::pending (deflate_stream.hpp:344-348)
-    if (!s || !s->is_deflate) return BPMD_R_INVALID_ARGUMENT;
-    if (value) *value = (unsigned)(s->pend.size() - s->pend_pos);
-    if (bits) *bits = (int)s->nbits;
-    return BPMD_OK;
+    return (!s || !s->is_deflate) ? BPMD_R_INVALID_ARGUMENT : s->def.w.pending(value, bits);
 }
 
 extern "C" int bpmd_deflate_stream_prime(bpmd_stream* s, int bits, int value)
 {
-    // deflate_stream::prime (deflate_stream.ipp:340-355): insert up to 16 bits
-    if (!s || !s->is_deflate) return BPMD_R_INVALID_ARGUMENT;
-    if (bits < 0 || bits > 16) return BPMD_NEED_BUFFERS;
-    init_deflate(s);   // maybe_init() (deflate_stream.ipp:560): a tune() after prime() is kept
-    if (bits) put_bits(s, (uint32_t)value & ((1u << bits) - 1u), (unsigned)bits);
-    return BPMD_OK;
+    return (!s || !s->is_deflate) ? BPMD_R_INVALID_ARGUMENT : s->def.w.prime(bits, value);
 }
 
 extern "C" int bpmd_inflate_stream_create(int window_bits, bpmd_stream** out)
@@ -450,7 +160,7 @@ extern "C" int bpmd_inflate_stream_create(int window_bits, bpmd_stream** out)
     bpmd_stream* s = new (std::nothrow) bpmd_stream();
     if (!s) return BPMD_R_INVALID_ARGUMENT;
     s->is_deflate = false;
-    s->inf_wbits = window_bits;
+    s->inf.wbits = window_bits;
     *out = s;
     return BPMD_R_OK;
 }
@@ -460,6 +170,7 @@ namespace {
 using bpmd::zst::Head;
 using bpmd::zst::Result;
 using bpmd::zst::State;
+using Inflate = bpmd_stream::Inflate;
 
 // inflate_stream::doReset (inflate_stream.ipp:55-72): HEAD, empty reservoir,
 // empty window of 2^windowBits
@@ -472,7 +183,7 @@ Head fresh_head(int window_bits)
 }
 
 // the stream's device state (reset if a reset() is pending)
-int ensure_zhead(bpmd_stream* s)
+int ensure_zhead(Inflate* s)
 {
     if (!s->zst) {
         if (hipMalloc(&s->zst, sizeof(State) + sizeof(Result)) != hipSuccess) {
@@ -482,7 +193,7 @@ int ensure_zhead(bpmd_stream* s)
         s->zreset = true;
     }
     if (s->zreset) {
-        const Head h = fresh_head(s->inf_wbits);
+        const Head h = fresh_head(s->wbits);
         if (hipMemcpy(s->zst, &h, sizeof h, hipMemcpyHostToDevice) != hipSuccess) return BPMD_R_HIP_ERROR;
         s->zreset = false;
     }
@@ -490,7 +201,7 @@ int ensure_zhead(bpmd_stream* s)
 }
 
 // ... and the single-call path's stream and input / output buffers
-int ensure_zbuf(bpmd_stream* s, size_t n_in, size_t cap)
+int ensure_zbuf(Inflate* s, size_t n_in, size_t cap)
 {
     if (!s->hs && hipStreamCreateWithFlags(&s->hs, hipStreamNonBlocking) != hipSuccess) return BPMD_R_HIP_ERROR;
     // input and output buffers, with slack for the 16-byte input staging loads
@@ -513,10 +224,26 @@ int ensure_zbuf(bpmd_stream* s, size_t n_in, size_t cap)
     return BPMD_R_OK;
 }
 
+// the stream's pinned staging buffer, at least `need` bytes
+uint8_t* pinned(Inflate* s, size_t need)
+{
+    if (need <= s->hpin_cap) return s->hpin;
+    if (s->hpin) (void)hipHostFree(s->hpin);
+    s->hpin = nullptr;
+    s->hpin_cap = 0;
+    const size_t c = std::max<size_t>(need + need / 2, 1 << 16);
+    if (hipHostMalloc((void**)&s->hpin, c, hipHostMallocDefault) != hipSuccess) {
+        s->hpin = nullptr;
+        return nullptr;
+    }
+    s->hpin_cap = c;
+    return s->hpin;
+}
+
 // one write() on the stream's own HIP stream: the input is uploaded, the
 // kernel runs, and the result record and output come back (the output
 // lands in the caller's buffer whether or not done() publishes it)
-int inflate_one(bpmd_stream* s, const uint8_t* in, size_t n, uint8_t* out, size_t cap, int flush, Result& res)
+int inflate_one(Inflate* s, const uint8_t* in, size_t n, uint8_t* out, size_t cap, int flush, Result& res)
 {
     int r = ensure_zbuf(s, n, cap);
     if (r) return r;
@@ -567,54 +294,25 @@ int inflate_one(bpmd_stream* s, const uint8_t* in, size_t n, uint8_t* out, size_
 // bytes do not depend on the batch's other messages.
 namespace {
 
-struct Job {
-    bpmd_stream* s = nullptr;
-    // inflate: the caller's input and output room
+// a queued call: its stream (one call per stream and batch), what the
+// direction's exec needs, and the call's return code
+struct InflateJob {
+    Inflate* s = nullptr;
+    // the caller's input and output room
     const uint8_t* in = nullptr;
     size_t n = 0;
     uint8_t* out = nullptr;
     size_t cap = 0;
     int flush = 0;
     Result res{};
-    // deflate: the stream's buffered input (s->in) and where its output goes
-    size_t out_cap = 0;
-    std::vector<uint8_t>* dout = nullptr;
-    int32_t status = 0;
-    uint32_t bits = 0;
     int rc = 0;
     bool done = false;
 };
-
-// a leader's device block, its pinned mirror and the HIP stream they use
-struct Arena {
-    hipStream_t hs = nullptr;
-    uint8_t* d = nullptr;
-    uint8_t* h = nullptr;
-    size_t cap = 0;
-    bool reserve(size_t need)
-    {
-        if (!hs && hipStreamCreateWithFlags(&hs, hipStreamNonBlocking) != hipSuccess) {
-            hs = nullptr;
-            return false;
-        }
-        if (need <= cap) return true;
-        if (d) (void)hipFree(d);
-        if (h) (void)hipHostFree(h);
-        d = h = nullptr;
-        cap = 0;
-        const size_t c = std::max<size_t>(need + need / 2, 1 << 20);
-        if (hipMalloc((void**)&d, c) != hipSuccess) {
-            d = nullptr;
-            return false;
-        }
-        if (hipHostMalloc((void**)&h, c, hipHostMallocDefault) != hipSuccess) {
-            (void)hipFree(d);
-            d = h = nullptr;
-            return false;
-        }
-        cap = c;
-        return true;
-    }
+struct DeflateJob {
+    const bpmd_stream* s = nullptr;
+    bpmd::DeflateStep* st = nullptr;
+    int rc = 0;
+    bool done = false;
 };
 
 // settings: max_calls < 2 is off
@@ -635,6 +333,7 @@ int batch_max()
     return m;
 }
 
+template <class Job>
 class Coalescer {
   public:
     explicit Coalescer(int dev) : dev_(dev) {}
@@ -686,38 +385,63 @@ class Coalescer {
     std::condition_variable done_, arrive_;
     std::deque<Job*> q_;
     bool busy_ = false;
-    Arena arena_;
+    Arena arena_{1 << 20};
     int dev_;
 };
 
-// one pair per device: a stream's device state lives on the device its
-// owner had current, and calls only batch with calls of the same device.
+// one per direction and device: a stream's device state lives on the device
+// its owner had current, and calls only batch with calls of the same device.
 // Process-lifetime objects (never destroyed: HIP may be torn down first).
 constexpr int MAX_DEV = 64;
-Coalescer* coalescer(int dev, bool inflate)
+template <class Job>
+Coalescer<Job>* coalescer(int dev)
 {
     static std::mutex mu;
-    static Coalescer* tab[2][MAX_DEV] = {};
+    static Coalescer<Job>* tab[MAX_DEV] = {};
     if (dev < 0 || dev >= MAX_DEV) return nullptr;
     std::lock_guard<std::mutex> lk(mu);
-    Coalescer*& c = tab[inflate ? 0 : 1][dev];
-    if (!c) c = new (std::nothrow) Coalescer(dev);
+    Coalescer<Job>*& c = tab[dev];
+    if (!c) c = new (std::nothrow) Coalescer<Job>(dev);
     return c;
 }
 
 constexpr size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 
+template <class Job>
 void fail_all(std::vector<Job*>& jobs, hipStream_t hs)
 {
     if (hs) (void)hipStreamSynchronize(hs);   // no DMA may still use the pinned mirror
     for (Job* j : jobs) j->rc = BPMD_R_HIP_ERROR;
 }
 
+// A batch's way back, after its copies in and its launch: one D2H of the
+// results at `at` (`head` bytes) and a wait; each call's used output then
+// follows in a copy of its own and a second wait, unless results and outputs
+// together (`all` bytes from `at`) are at most 4 MiB and came with the first.
+// used(i, len, room): call i's output length and room, read from the results
+// in the pinned mirror; off[i]: its output's place in the block.
+template <class Used>
+bool read_back(Arena& A, size_t at, size_t head, size_t all, const std::vector<size_t>& off, Used&& used)
+{
+    const bool whole = all <= (4u << 20);
+    bool ok = hipMemcpyAsync(A.h + at, A.d + at, whole ? all : head, hipMemcpyDeviceToHost, A.hs) == hipSuccess &&
+              hipStreamSynchronize(A.hs) == hipSuccess;
+    for (size_t i = 0; i < off.size() && ok; ++i) {
+        size_t len = 0, room = 0;
+        used(i, len, room);
+        ok = len <= room;
+        if (ok && !whole && len)
+            ok = hipMemcpyAsync(A.h + off[i], A.d + off[i], len, hipMemcpyDeviceToHost, A.hs) == hipSuccess;
+    }
+    if (ok && !whole) ok = hipStreamSynchronize(A.hs) == hipSuccess;
+    return ok;
+}
+
 // k inflate write() calls as one launch.  Block: [ZCall k][inputs]
 // [Result k][outputs]; one H2D of calls + inputs, the launch, one D2H of the
 // results and outputs (of the results alone, then each call's used output,
 // when the output room is over 4 MiB).
-void inflate_batch(Arena& A, std::vector<Job*>& jobs)
+void inflate_batch(Arena& A, std::vector<InflateJob*>& jobs)
 {
     using bpmd::zst::ZCall;
     const uint32_t k = (uint32_t)jobs.size();
@@ -739,7 +463,7 @@ void inflate_batch(Arena& A, std::vector<Job*>& jobs)
     if (!A.reserve(total)) return fail_all(jobs, A.hs);
     ZCall* zc = (ZCall*)A.h;
     for (uint32_t i = 0; i < k; ++i) {
-        const Job* j = jobs[i];
+        const InflateJob* j = jobs[i];
         if (j->n) std::memcpy(A.h + ioff[i], j->in, j->n);
         ZCall c{};
         c.st = j->s->zst;
@@ -751,25 +475,16 @@ void inflate_batch(Arena& A, std::vector<Job*>& jobs)
         c.flush = j->flush;
         zc[i] = c;
     }
-    const bool whole = total - res_at <= (4u << 20);
-    bool ok = hipMemcpyAsync(A.d, A.h, res_at, hipMemcpyHostToDevice, A.hs) == hipSuccess &&
-              bpmd_internal_zstream_write_batch(A.d, k, A.hs) == 0 &&
-              hipMemcpyAsync(A.h + res_at, A.d + res_at, (whole ? total : res_at + 64ull * k) - res_at,
-                             hipMemcpyDeviceToHost, A.hs) == hipSuccess &&
-              hipStreamSynchronize(A.hs) == hipSuccess;
-    if (!ok) return fail_all(jobs, A.hs);
-    for (uint32_t i = 0; i < k && ok; ++i) {
-        Job* j = jobs[i];
-        std::memcpy(&j->res, A.h + res_at + 64ull * i, sizeof(Result));
-        ok = j->res.out_used <= j->cap;
-        if (ok && !whole && j->res.out_used)
-            ok = hipMemcpyAsync(A.h + ooff[i], A.d + ooff[i], j->res.out_used, hipMemcpyDeviceToHost, A.hs) ==
-                 hipSuccess;
-    }
-    if (ok && !whole) ok = hipStreamSynchronize(A.hs) == hipSuccess;
+    const bool ok = hipMemcpyAsync(A.d, A.h, res_at, hipMemcpyHostToDevice, A.hs) == hipSuccess &&
+                    bpmd_internal_zstream_write_batch(A.d, k, A.hs) == 0 &&
+                    read_back(A, res_at, 64ull * k, total - res_at, ooff, [&](size_t i, size_t& len, size_t& room) {
+                        std::memcpy(&jobs[i]->res, A.h + res_at + 64ull * i, sizeof(Result));
+                        len = jobs[i]->res.out_used;
+                        room = jobs[i]->cap;
+                    });
     if (!ok) return fail_all(jobs, A.hs);
     for (uint32_t i = 0; i < k; ++i) {
-        Job* j = jobs[i];
+        InflateJob* j = jobs[i];
         if (j->res.out_used) std::memcpy(j->out, A.h + ooff[i], j->res.out_used);
         j->rc = BPMD_R_OK;
     }
@@ -778,108 +493,97 @@ void inflate_batch(Arena& A, std::vector<Job*>& jobs)
 // (a batch of one too: with the batcher on, streams use the leaders'
 // buffers and HIP stream and allocate none of their own -- creating a HIP
 // stream or pinned buffer per connection serializes in the runtime)
-void inflate_exec(Arena& A, std::vector<Job*>& jobs)
+void inflate_exec(Arena& A, std::vector<InflateJob*>& jobs)
 {
     g_bstat[1].fetch_add(1);
     inflate_batch(A, jobs);
 }
 
-// deflate flushes with the same parameters (level, windowBits, strategy,
-// tune values, history or not) as one call of the deflater.  Block:
-// [SoA meta][outputs][history + input, per flush]; H2D of meta and inputs,
-// the kernels (the chunk count is known here: nothing is read back), one D2H
-// of meta + outputs (meta, then each flush's output, past 4 MiB of room).
-void deflate_group(Arena& A, std::vector<Job*>& jobs)
+// The deflate transport: flushes with the same parameters (level,
+// windowBits, strategy, tune values, history or not) as one call of the
+// deflater.  Block: [SoA meta][outputs][history + input, per flush]; H2D of
+// meta and inputs, the kernels (the chunk count is known here: nothing is
+// read back), one D2H of meta + outputs (meta, then each flush's output, past
+// 4 MiB of room).
+void deflate_group(Arena& A, std::vector<DeflateJob*>& jobs)
 {
     const uint32_t k = (uint32_t)jobs.size();
-    const bpmd_stream* s0 = jobs[0]->s;
-    const bool hist = !s0->hist.empty();
+    const bpmd::DeflateStep& s0 = *jobs[0]->st;
+    const bool hist = s0.hist_len != 0;
     const size_t m_in_off = 0, m_out_off = 8ull * k, m_in_len = 16ull * k, m_out_cap = 20ull * k,
                  m_hist = 24ull * k, m_out_len = 28ull * k, m_bits = 32ull * k, m_status = 36ull * k;
     const size_t out_at = up256(40ull * k);
-    std::vector<uint64_t> oo(k), io(k);
-    size_t o = 0;
+    std::vector<size_t> oo(k), io(k);   // in the block; in the inputs
+    size_t o = out_at;
     for (uint32_t i = 0; i < k; ++i) {
         oo[i] = o;
-        o = up256(o + jobs[i]->out_cap);
+        o = up256(o + jobs[i]->st->out_cap);
     }
-    const size_t in_at = out_at + o;
+    const size_t in_at = o;
     size_t ib = 0;
     int64_t chunks = 0;
     for (uint32_t i = 0; i < k; ++i) {
-        const bpmd_stream* s = jobs[i]->s;
-        const size_t hn = s->hist.size(), n = s->in.size();
-        if (n + hn > 0xFFFFFFFFu || jobs[i]->out_cap > 0xFFFFFFFFu) {
-            for (Job* j : jobs) j->rc = BPMD_R_INVALID_ARGUMENT;
+        const bpmd::DeflateStep& s = *jobs[i]->st;
+        if (s.n + s.hist_len > 0xFFFFFFFFu || s.out_cap > 0xFFFFFFFFu) {
+            for (DeflateJob* j : jobs) j->rc = BPMD_R_INVALID_ARGUMENT;
             return;
         }
         io[i] = ib;
-        ib = up256(ib + hn + n);
-        // run_one's count (pmd_deflate.hip chunk_count)
-        chunks += hn ? (int64_t)((n + 4095) / 4096) : (n > 4096 ? (int64_t)((n + 4095) / 4096) : 0);
+        ib = up256(ib + s.hist_len + s.n);
+        chunks += bpmd::deflate_chunks((uint32_t)s.n, s.hist_len != 0);
     }
     const size_t total = in_at + ib + 16;
     if (!A.reserve(total)) return fail_all(jobs, A.hs);
     uint8_t* h = A.h;
     std::memset(h, 0, out_at);
     for (uint32_t i = 0; i < k; ++i) {
-        const bpmd_stream* s = jobs[i]->s;
-        const size_t hn = s->hist.size(), n = s->in.size();
-        ((uint64_t*)(h + m_in_off))[i] = io[i] + hn;
-        ((uint64_t*)(h + m_out_off))[i] = oo[i];
-        ((uint32_t*)(h + m_in_len))[i] = (uint32_t)n;
-        ((uint32_t*)(h + m_out_cap))[i] = (uint32_t)jobs[i]->out_cap;
-        ((uint32_t*)(h + m_hist))[i] = (uint32_t)hn;
-        if (hn) std::memcpy(h + in_at + io[i], s->hist.data(), hn);
-        if (n) std::memcpy(h + in_at + io[i] + hn, s->in.data(), n);
+        const bpmd::DeflateStep& s = *jobs[i]->st;
+        ((uint64_t*)(h + m_in_off))[i] = io[i] + s.hist_len;
+        ((uint64_t*)(h + m_out_off))[i] = oo[i] - out_at;
+        ((uint32_t*)(h + m_in_len))[i] = (uint32_t)s.n;
+        ((uint32_t*)(h + m_out_cap))[i] = (uint32_t)s.out_cap;
+        ((uint32_t*)(h + m_hist))[i] = (uint32_t)s.hist_len;
+        if (s.hist_len) std::memcpy(h + in_at + io[i], s.hist, s.hist_len);
+        if (s.n) std::memcpy(h + in_at + io[i] + s.hist_len, s.in, s.n);
     }
     uint8_t* d = A.d;
-    const bool whole = in_at <= (4u << 20);
     const bpmd::Batch b{d + in_at, (const uint64_t*)(d + m_in_off), (const uint32_t*)(d + m_in_len), k, d + out_at,
                         (const uint64_t*)(d + m_out_off), (const uint32_t*)(d + m_out_cap), (uint32_t*)(d + m_out_len),
                         (int32_t*)(d + m_status)};
-    bool ok = hipMemcpyAsync(d, h, out_at, hipMemcpyHostToDevice, A.hs) == hipSuccess &&
-              (ib == 0 || hipMemcpyAsync(d + in_at, h + in_at, ib, hipMemcpyHostToDevice, A.hs) == hipSuccess) &&
-              bpmd::deflate_bits_hist(b, (uint32_t*)(d + m_bits), hist ? (const uint32_t*)(d + m_hist) : nullptr,
-                                      s0->level, s0->wbits, s0->strategy, s0->tuned ? s0->tune4 : nullptr, A.hs,
-                                      chunks) == 0 &&
-              hipMemcpyAsync(h, d, whole ? in_at : out_at, hipMemcpyDeviceToHost, A.hs) == hipSuccess &&
-              hipStreamSynchronize(A.hs) == hipSuccess;
-    if (!ok) return fail_all(jobs, A.hs);
-    for (uint32_t i = 0; i < k && ok; ++i) {
-        const uint32_t len = ((const uint32_t*)(h + m_out_len))[i];
-        ok = len <= jobs[i]->out_cap;
-        if (ok && !whole && len)
-            ok = hipMemcpyAsync(h + out_at + oo[i], d + out_at + oo[i], len, hipMemcpyDeviceToHost, A.hs) ==
-                 hipSuccess;
-    }
-    if (ok && !whole) ok = hipStreamSynchronize(A.hs) == hipSuccess;
+    const bool ok =
+        hipMemcpyAsync(d, h, out_at, hipMemcpyHostToDevice, A.hs) == hipSuccess &&
+        (ib == 0 || hipMemcpyAsync(d + in_at, h + in_at, ib, hipMemcpyHostToDevice, A.hs) == hipSuccess) &&
+        bpmd::deflate_bits_hist(b, (uint32_t*)(d + m_bits), hist ? (const uint32_t*)(d + m_hist) : nullptr, s0.level,
+                                s0.wbits, s0.strategy, s0.tune, A.hs, chunks) == 0 &&
+        read_back(A, 0, out_at, in_at, oo, [&](size_t i, size_t& len, size_t& room) {
+            len = ((const uint32_t*)(h + m_out_len))[i];
+            room = jobs[i]->st->out_cap;
+        });
     if (!ok) return fail_all(jobs, A.hs);
     for (uint32_t i = 0; i < k; ++i) {
-        Job* j = jobs[i];
+        DeflateJob* j = jobs[i];
         const uint32_t len = ((const uint32_t*)(h + m_out_len))[i];
-        j->dout->assign(h + out_at + oo[i], h + out_at + oo[i] + len);
-        j->status = ((const int32_t*)(h + m_status))[i];
-        j->bits = ((const uint32_t*)(h + m_bits))[i];
+        j->st->out.assign(h + oo[i], h + oo[i] + len);
+        j->st->status = ((const int32_t*)(h + m_status))[i];
+        j->st->bits = ((const uint32_t*)(h + m_bits))[i];
         j->rc = BPMD_R_OK;
     }
 }
 
-bool same_params(const bpmd_stream* a, const bpmd_stream* b)
+bool same_params(const bpmd::DeflateStep& a, const bpmd::DeflateStep& b)
 {
-    return a->level == b->level && a->wbits == b->wbits && a->strategy == b->strategy && a->tuned == b->tuned &&
-           (!a->tuned || std::memcmp(a->tune4, b->tune4, sizeof a->tune4) == 0) &&
-           a->hist.empty() == b->hist.empty();
+    return a.level == b.level && a.wbits == b.wbits && a.strategy == b.strategy && !a.tune == !b.tune &&
+           (!a.tune || std::memcmp(a.tune, b.tune, 4 * sizeof(int)) == 0) && !a.hist_len == !b.hist_len;
 }
 
-void deflate_exec(Arena& A, std::vector<Job*>& jobs)
+void deflate_exec(Arena& A, std::vector<DeflateJob*>& jobs)
 {
     std::vector<bool> used(jobs.size(), false);
     for (size_t i = 0; i < jobs.size(); ++i) {
         if (used[i]) continue;
-        std::vector<Job*> g{jobs[i]};
+        std::vector<DeflateJob*> g{jobs[i]};
         for (size_t j = i + 1; j < jobs.size(); ++j)
-            if (!used[j] && same_params(jobs[i]->s, jobs[j]->s)) {
+            if (!used[j] && same_params(*jobs[i]->st, *jobs[j]->st)) {
                 used[j] = true;
                 g.push_back(jobs[j]);
             }
@@ -889,12 +593,12 @@ void deflate_exec(Arena& A, std::vector<Job*>& jobs)
 }
 
 // the inflate write()'s call, batched or not
-int inflate_call(bpmd_stream* s, const uint8_t* in, size_t n, uint8_t* out, size_t cap, int flush, Result& res)
+int inflate_call(Inflate* s, const uint8_t* in, size_t n, uint8_t* out, size_t cap, int flush, Result& res)
 {
     const int mx = batch_max();
     if (mx < 2) return inflate_one(s, in, n, out, cap, flush, res);
     g_bstat[0].fetch_add(1);
-    Job j;
+    InflateJob j;
     j.s = s;
     j.in = in;
     j.n = n;
@@ -902,28 +606,36 @@ int inflate_call(bpmd_stream* s, const uint8_t* in, size_t n, uint8_t* out, size
     j.cap = cap;
     j.flush = flush;
     int dev = 0;
-    Coalescer* c = hipGetDevice(&dev) == hipSuccess ? coalescer(dev, true) : nullptr;
+    Coalescer<InflateJob>* c = hipGetDevice(&dev) == hipSuccess ? coalescer<InflateJob>(dev) : nullptr;
     if (!c) return inflate_one(s, in, n, out, cap, flush, res);
     c->run(&j, mx, inflate_exec);
     res = j.res;
     return j.rc;
 }
 
-int run_flush(bpmd_stream* s, size_t out_cap, std::vector<uint8_t>& out, int32_t& status, uint32_t& bits)
+// the writer's device step (deflate_writer.h): through the coalescer, or with
+// the batcher off as a group of one on the stream's own arena
+int run_flush(void* stream, bpmd::DeflateStep& st)
 {
-    const int mx = batch_max();
-    if (mx < 2) return run_one(s, s->in.data(), s->in.size(), out_cap, out, status, bits);
-    g_bstat[2].fetch_add(1);
-    Job j;
+    bpmd_stream* s = (bpmd_stream*)stream;
+    DeflateJob j;
     j.s = s;
-    j.out_cap = out_cap;
-    j.dout = &out;
-    int dev = 0;
-    Coalescer* c = hipGetDevice(&dev) == hipSuccess ? coalescer(dev, false) : nullptr;
-    if (!c) return run_one(s, s->in.data(), s->in.size(), out_cap, out, status, bits);
-    c->run(&j, mx, deflate_exec);
-    status = j.status;
-    bits = j.bits;
+    j.st = &st;
+    const int mx = batch_max();
+    Coalescer<DeflateJob>* c = nullptr;
+    if (mx >= 2) {
+        g_bstat[2].fetch_add(1);
+        int dev = 0;
+        if (hipGetDevice(&dev) == hipSuccess) c = coalescer<DeflateJob>(dev);
+    }
+    if (c) {
+        c->run(&j, mx, deflate_exec);
+        return j.rc;
+    }
+    const int r = bpmd_init();
+    if (r) return r;
+    std::vector<DeflateJob*> one{&j};
+    deflate_group(s->def.arena, one);
     return j.rc;
 }
 
@@ -957,8 +669,8 @@ extern "C" int bpmd_inflate_stream_reset(bpmd_stream* s, int window_bits)
 {
     if (!s || s->is_deflate) return BPMD_R_INVALID_ARGUMENT;
     if (window_bits < 8 || window_bits > 15) return BPMD_R_DOMAIN_ERROR;
-    s->inf_wbits = window_bits;
-    s->zreset = true;   // applied before the next write()
+    s->inf.wbits = window_bits;
+    s->inf.zreset = true;   // applied before the next write()
     return BPMD_R_OK;
 }
 
@@ -983,9 +695,10 @@ extern "C" int bpmd_inflate_stream_write(bpmd_stream* s, bpmd_zparams* zs, int f
     // reference's "avail_out >= 258" fast-path test unchanged.
     const size_t bound = 1040 * n + 8192;
     const size_t cap = std::min<size_t>(zs->avail_out, bound);
-    if ((r = ensure_zhead(s)) != 0) return r;
+    if ((r = ensure_zhead(&s->inf)) != 0) return r;
     Result res{};
-    if ((r = inflate_call(s, (const uint8_t*)zs->next_in, n, (uint8_t*)zs->next_out, cap, flush, res)) != 0) return r;
+    if ((r = inflate_call(&s->inf, (const uint8_t*)zs->next_in, n, (uint8_t*)zs->next_out, cap, flush, res)) != 0)
+        return r;
     if (res.published) {
         zs->next_in = (const uint8_t*)zs->next_in + res.in_used;
         zs->avail_in -= res.in_used;
@@ -1002,23 +715,26 @@ extern "C" int bpmd_inflate_stream_footprint(const bpmd_stream* s, size_t* host_
 {
     if (!s || s->is_deflate) return BPMD_R_INVALID_ARGUMENT;
     if (device_bytes)
-        *device_bytes = (s->zst ? sizeof(State) + sizeof(Result) : 0) + s->din_cap + s->dout_cap;
-    if (host_bytes) *host_bytes = s->hpin_cap;   // pinned staging only
+        *device_bytes = (s->inf.zst ? sizeof(State) + sizeof(Result) : 0) + s->inf.din_cap + s->inf.dout_cap;
+    if (host_bytes) *host_bytes = s->inf.hpin_cap;   // pinned staging only
     return BPMD_R_OK;
 }
 
 extern "C" void bpmd_stream_destroy(bpmd_stream* s)
 {
     if (!s) return;
-    if (s->hs) (void)hipStreamSynchronize(s->hs);
-    if (s->dmem) (void)hipFree(s->dmem);
-    if (s->zst) (void)hipFree(s->zst);
-    if (s->din) (void)hipFree(s->din);
-    if (s->dout) (void)hipFree(s->dout);
-    if (s->hpin) (void)hipHostFree(s->hpin);
-    if (s->hs) {
-        bpmd_internal_scratch_release(s->hs);
-        (void)hipStreamDestroy(s->hs);
-    }
+    const Arena& A = s->def.arena;
+    const Inflate& I = s->inf;
+    for (hipStream_t hs : {A.hs, I.hs})
+        if (hs) (void)hipStreamSynchronize(hs);
+    for (void* p : {(void*)A.d, I.zst, (void*)I.din, (void*)I.dout})
+        if (p) (void)hipFree(p);
+    for (void* p : {(void*)A.h, (void*)I.hpin})
+        if (p) (void)hipHostFree(p);
+    for (hipStream_t hs : {A.hs, I.hs})
+        if (hs) {
+            bpmd_internal_scratch_release(hs);
+            (void)hipStreamDestroy(hs);
+        }
     delete s;
 }

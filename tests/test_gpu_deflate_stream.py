@@ -2,7 +2,10 @@
 through the scripts of tests/deflate_scripts.py beside the oracle backend
 (Beast's deflate_stream restated): every Flush value, params(), tune(),
 prime() and pending(), at levels 0-9, windowBits 9 / 10 / 15 and every
-strategy, with the stream batcher off (run_one) and on (deflate_group).
+strategy, with the stream batcher off ("unbatched": each flush is a
+deflate_group of one on the stream's own arena) and on ("batched": the
+coalescer's groups on its leader's arena).  The call protocol alone, without
+a device, is tests/test_deflate_writer.py.
 
 A  call parity: per step the return code, avail_in and total_in equal the
    oracle backend's on the same script, and pending() after prime().
