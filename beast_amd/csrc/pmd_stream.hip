@@ -3,17 +3,17 @@
 // zlib::deflate_stream / zlib::inflate_stream write() semantics, executed by
 // the GPU kernels.  Host code only.
 //
-// deflate: the call protocol is deflate_writer.h (no HIP in it); here is its
-//   device step, one transport for a flush alone and for a batch of them
-//   (deflate_group), and the C ABI's forwards.
-// inflate: the reference's decoder state lives on the device (zstream.h) and
-//   each write() is one launch of the per-stream kernel (pmd_zstream.hip),
+// The C ABI's forwards, the two call protocols' device steps, one Arena and
+// two transports, each for a call alone and for a batch of them.
+// deflate: the call protocol is deflate_writer.h (no HIP in it); its step
+//   compresses a flush's bytes (deflate_group).
+// inflate: the call protocol is inflate_reader.h (no HIP in it).  The
+//   reference's decoder state lives on the device (zstream.h) and each
+//   write() is one workgroup of the per-stream kernel (pmd_zstream.hip),
 //   which runs inflate_stream.ipp's state machine with its bit reservoir and
-//   window: the call uploads the caller's input, the kernel decodes exactly
-//   what the reference would, and the host copies the output back and
-//   advances z_params by the kernel's done() record -- the reference's
-//   total_in (input left unconsumed stays with the caller), total_out and
-//   data_type; an error returns without advancing them, as err() does.
+//   window: the step uploads the caller's input, the kernel decodes exactly
+//   what the reference would, and the output and the kernel's done() record
+//   come back (inflate_batch).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -29,13 +29,14 @@
 
 #include "../../include/beast_pmd.h"
 #include "deflate_writer.h"
+#include "inflate_reader.h"
 #include "pmd_internal.h"
 #include "zstream.h"
 
 namespace {
 
 // a device block, its pinned mirror and the HIP stream they use: a
-// coalescer's leader's, or a deflate stream's own when the batcher is off
+// coalescer's leader's, or a stream's own when the batcher is off
 struct Arena {
     hipStream_t hs = nullptr;
     uint8_t* d = nullptr;
@@ -71,35 +72,21 @@ struct Arena {
 
 }  // namespace
 
+// a deflater or an inflater
 struct bpmd_stream {
     bool is_deflate = true;
-    struct Deflate {
-        bpmd::DeflateWriter w;
-        // the batcher off: the stream's own block (64 KiB at least: a server
-        // may hold thousands of these), made by its first flush
-        Arena arena{1 << 16};
-    } def;
-    struct Inflate {
-        // windowBits, device state (zstream.h State + Result), call buffers
-        int wbits = 15;
-        void* zst = nullptr;
-        bool zreset = true;         // a reset() to apply before the next write()
-        uint8_t* din = nullptr;
-        size_t din_cap = 0;
-        uint8_t* dout = nullptr;
-        size_t dout_cap = 0;
-        // the batcher off: the stream's HIP stream and its pinned host staging
-        // for the call's copies (a copy from pageable memory is staged by the
-        // runtime and waits; from pinned memory it is one DMA)
-        hipStream_t hs = nullptr;
-        uint8_t* hpin = nullptr;
-        size_t hpin_cap = 0;
-    } inf;
+    bpmd::DeflateWriter def;
+    bpmd::InflateReader inf;
+    void* zst = nullptr;   // inflate: the device state (zstream.h State + Result)
+    // the batcher off: the stream's own block (64 KiB at least: a server may
+    // hold thousands of these), made by its first flush or write
+    Arena arena{1 << 16};
 };
 
 namespace {
 
 int run_flush(void* stream, bpmd::DeflateStep& st);
+int run_inflate(void* stream, bpmd::InflateStep& st);
 
 }  // namespace
 
@@ -110,59 +97,79 @@ extern "C" int bpmd_deflate_stream_create(int level, int window_bits, int mem_le
     *out = nullptr;
     bpmd_stream* s = new (std::nothrow) bpmd_stream();
     if (!s) return BPMD_R_INVALID_ARGUMENT;
-    const int r = s->def.w.create(level, window_bits, mem_level, strategy);
+    const int r = s->def.create(level, window_bits, mem_level, strategy);
     if (r) {
         delete s;
         return r;
     }
-    s->def.w.compress = run_flush;
-    s->def.w.ctx = s;
+    s->def.compress = run_flush;
+    s->def.ctx = s;
     *out = s;
     return BPMD_R_OK;
 }
 
 extern "C" int bpmd_deflate_stream_reset(bpmd_stream* s)
 {
-    return (!s || !s->is_deflate) ? BPMD_R_INVALID_ARGUMENT : s->def.w.reset();
+    return (!s || !s->is_deflate) ? BPMD_R_INVALID_ARGUMENT : s->def.reset();
 }
 
 extern "C" int bpmd_deflate_stream_write(bpmd_stream* s, bpmd_zparams* zs, int flush)
 {
-    return (!s || !s->is_deflate || !zs) ? BPMD_R_INVALID_ARGUMENT : s->def.w.write(zs, flush);
+    return (!s || !s->is_deflate || !zs) ? BPMD_R_INVALID_ARGUMENT : s->def.write(zs, flush);
 }
 
 extern "C" int bpmd_deflate_stream_params(bpmd_stream* s, bpmd_zparams* zs, int level, int strategy)
 {
-    return (!s || !s->is_deflate || !zs) ? BPMD_R_INVALID_ARGUMENT : s->def.w.params(zs, level, strategy);
+    return (!s || !s->is_deflate || !zs) ? BPMD_R_INVALID_ARGUMENT : s->def.params(zs, level, strategy);
 }
 
 extern "C" int bpmd_deflate_stream_tune(bpmd_stream* s, int good_length, int max_lazy, int nice_length, int max_chain)
 {
     return (!s || !s->is_deflate) ? BPMD_R_INVALID_ARGUMENT
-                                  : s->def.w.tune(good_length, max_lazy, nice_length, max_chain);
+                                  : s->def.tune(good_length, max_lazy, nice_length, max_chain);
 }
 
 extern "C" int bpmd_deflate_stream_pending(bpmd_stream* s, unsigned* value, int* bits)
 {
-    return (!s || !s->is_deflate) ? BPMD_R_INVALID_ARGUMENT : s->def.w.pending(value, bits);
+    return (!s || !s->is_deflate) ? BPMD_R_INVALID_ARGUMENT : s->def.pending(value, bits);
 }
 
 extern "C" int bpmd_deflate_stream_prime(bpmd_stream* s, int bits, int value)
 {
-    return (!s || !s->is_deflate) ? BPMD_R_INVALID_ARGUMENT : s->def.w.prime(bits, value);
+    return (!s || !s->is_deflate) ? BPMD_R_INVALID_ARGUMENT : s->def.prime(bits, value);
 }
 
 extern "C" int bpmd_inflate_stream_create(int window_bits, bpmd_stream** out)
 {
     if (!out) return BPMD_R_INVALID_ARGUMENT;
     *out = nullptr;
-    if (window_bits < 8 || window_bits > 15) return BPMD_R_DOMAIN_ERROR;   // inflate_stream.ipp:57-61
     bpmd_stream* s = new (std::nothrow) bpmd_stream();
     if (!s) return BPMD_R_INVALID_ARGUMENT;
+    const int r = s->inf.create(window_bits);
+    if (r) {
+        delete s;
+        return r;
+    }
     s->is_deflate = false;
-    s->inf.wbits = window_bits;
+    s->inf.run = run_inflate;
+    s->inf.ctx = s;
     *out = s;
     return BPMD_R_OK;
+}
+
+extern "C" int bpmd_inflate_stream_reset(bpmd_stream* s, int window_bits)
+{
+    return (!s || s->is_deflate) ? BPMD_R_INVALID_ARGUMENT : s->inf.reset(window_bits);
+}
+
+extern "C" int bpmd_inflate_stream_clear(bpmd_stream* s)
+{
+    return (!s || s->is_deflate) ? BPMD_R_INVALID_ARGUMENT : s->inf.clear();
+}
+
+extern "C" int bpmd_inflate_stream_write(bpmd_stream* s, bpmd_zparams* zs, int flush)
+{
+    return (!s || s->is_deflate) ? BPMD_R_INVALID_ARGUMENT : s->inf.write(zs, flush);
 }
 
 namespace {
@@ -170,7 +177,6 @@ namespace {
 using bpmd::zst::Head;
 using bpmd::zst::Result;
 using bpmd::zst::State;
-using Inflate = bpmd_stream::Inflate;
 
 // inflate_stream::doReset (inflate_stream.ipp:55-72): HEAD, empty reservoir,
 // empty window of 2^windowBits
@@ -182,96 +188,20 @@ Head fresh_head(int window_bits)
     return h;
 }
 
-// the stream's device state (reset if a reset() is pending)
-int ensure_zhead(Inflate* s)
+// the stream's device state, and the step's pending reset applied to it
+int ensure_zhead(bpmd_stream* s, bpmd::InflateStep& st)
 {
     if (!s->zst) {
         if (hipMalloc(&s->zst, sizeof(State) + sizeof(Result)) != hipSuccess) {
             s->zst = nullptr;
             return BPMD_R_HIP_ERROR;
         }
-        s->zreset = true;
+        st.reset = true;
     }
-    if (s->zreset) {
-        const Head h = fresh_head(s->wbits);
+    if (st.reset) {
+        const Head h = fresh_head(st.wbits);
         if (hipMemcpy(s->zst, &h, sizeof h, hipMemcpyHostToDevice) != hipSuccess) return BPMD_R_HIP_ERROR;
-        s->zreset = false;
-    }
-    return BPMD_R_OK;
-}
-
-// ... and the single-call path's stream and input / output buffers
-int ensure_zbuf(Inflate* s, size_t n_in, size_t cap)
-{
-    if (!s->hs && hipStreamCreateWithFlags(&s->hs, hipStreamNonBlocking) != hipSuccess) return BPMD_R_HIP_ERROR;
-    // input and output buffers, with slack for the 16-byte input staging loads
-    if (n_in + 64 > s->din_cap) {
-        if (s->din) (void)hipFree(s->din);
-        s->din = nullptr;
-        s->din_cap = 0;
-        const size_t c = std::max<size_t>(n_in + n_in / 2 + 64, 4096);
-        if (hipMalloc(&s->din, c) != hipSuccess) return BPMD_R_HIP_ERROR;
-        s->din_cap = c;
-    }
-    if (cap + 128 > s->dout_cap) {   // [result 64 B][output]
-        if (s->dout) (void)hipFree(s->dout);
-        s->dout = nullptr;
-        s->dout_cap = 0;
-        const size_t c = std::max<size_t>(cap + cap / 2 + 128, 4096);
-        if (hipMalloc(&s->dout, c) != hipSuccess) return BPMD_R_HIP_ERROR;
-        s->dout_cap = c;
-    }
-    return BPMD_R_OK;
-}
-
-// the stream's pinned staging buffer, at least `need` bytes
-uint8_t* pinned(Inflate* s, size_t need)
-{
-    if (need <= s->hpin_cap) return s->hpin;
-    if (s->hpin) (void)hipHostFree(s->hpin);
-    s->hpin = nullptr;
-    s->hpin_cap = 0;
-    const size_t c = std::max<size_t>(need + need / 2, 1 << 16);
-    if (hipHostMalloc((void**)&s->hpin, c, hipHostMallocDefault) != hipSuccess) {
-        s->hpin = nullptr;
-        return nullptr;
-    }
-    s->hpin_cap = c;
-    return s->hpin;
-}
-
-// one write() on the stream's own HIP stream: the input is uploaded, the
-// kernel runs, and the result record and output come back (the output
-// lands in the caller's buffer whether or not done() publishes it)
-int inflate_one(Inflate* s, const uint8_t* in, size_t n, uint8_t* out, size_t cap, int flush, Result& res)
-{
-    int r = ensure_zbuf(s, n, cap);
-    if (r) return r;
-    const hipStream_t hs = s->hs;
-    // the result record and the output share one device block, so one D2H
-    // brings both back when the output is at most `spec` bytes (pinned
-    // staging for both directions: each copy is one DMA)
-    constexpr size_t RES_AT = 64;
-    const size_t spec = std::min<size_t>(cap, 16384);
-    uint8_t* h = pinned(s, std::max(n, RES_AT + spec) + 64);
-    if (!h) return BPMD_R_HIP_ERROR;
-    if (n) std::memcpy(h, in, n);
-    bool ok = (n == 0 || hipMemcpyAsync(s->din, h, n, hipMemcpyHostToDevice, hs) == hipSuccess) &&
-              bpmd_internal_zstream_write(s->zst, s->din, n, s->dout + RES_AT, cap, flush, s->dout, hs) == 0 &&
-              hipMemcpyAsync(h, s->dout, RES_AT + spec, hipMemcpyDeviceToHost, hs) == hipSuccess &&
-              hipStreamSynchronize(hs) == hipSuccess;
-    if (ok) std::memcpy(&res, h, sizeof res);
-    ok = ok && res.out_used <= cap;
-    if (ok && res.out_used) {
-        std::memcpy(out, h + RES_AT, std::min<size_t>(res.out_used, spec));
-        if (res.out_used > spec)
-            ok = hipMemcpy(out + spec, s->dout + RES_AT + spec, res.out_used - spec, hipMemcpyDeviceToHost) ==
-                 hipSuccess;
-    }
-    if (!ok) {
-        // the pinned staging buffer may still be a DMA's source or target
-        (void)hipStreamSynchronize(hs);
-        return BPMD_R_HIP_ERROR;   // the device state is unchanged only if the kernel never ran
+        st.reset = false;
     }
     return BPMD_R_OK;
 }
@@ -294,26 +224,17 @@ int inflate_one(Inflate* s, const uint8_t* in, size_t n, uint8_t* out, size_t ca
 // bytes do not depend on the batch's other messages.
 namespace {
 
-// a queued call: its stream (one call per stream and batch), what the
-// direction's exec needs, and the call's return code
-struct InflateJob {
-    Inflate* s = nullptr;
-    // the caller's input and output room
-    const uint8_t* in = nullptr;
-    size_t n = 0;
-    uint8_t* out = nullptr;
-    size_t cap = 0;
-    int flush = 0;
-    Result res{};
-    int rc = 0;
-    bool done = false;
-};
-struct DeflateJob {
+// a queued call: its stream (one call per stream and batch), the protocol's
+// step record, and the call's return code
+template <class Step>
+struct Job {
     const bpmd_stream* s = nullptr;
-    bpmd::DeflateStep* st = nullptr;
+    Step* st = nullptr;
     int rc = 0;
     bool done = false;
 };
+using InflateJob = Job<bpmd::InflateStep>;
+using DeflateJob = Job<bpmd::DeflateStep>;
 
 // settings: max_calls < 2 is off
 std::atomic<int> g_bmax{-1}, g_bdelay{-1};
@@ -437,10 +358,11 @@ bool read_back(Arena& A, size_t at, size_t head, size_t all, const std::vector<s
     return ok;
 }
 
-// k inflate write() calls as one launch.  Block: [ZCall k][inputs]
-// [Result k][outputs]; one H2D of calls + inputs, the launch, one D2H of the
-// results and outputs (of the results alone, then each call's used output,
-// when the output room is over 4 MiB).
+// The inflate transport: k write() calls as one launch (a call alone is k = 1).
+// Block: [ZCall k][inputs][Result k][outputs]; one H2D of calls + inputs, the
+// launch, one D2H of the results and outputs (of the results alone, then each
+// call's used output, when the output room is over 4 MiB).  The output lands
+// in the caller's buffer whether or not done() publishes it.
 void inflate_batch(Arena& A, std::vector<InflateJob*>& jobs)
 {
     using bpmd::zst::ZCall;
@@ -451,48 +373,50 @@ void inflate_batch(Arena& A, std::vector<InflateJob*>& jobs)
     size_t o = up256(sizeof(ZCall) * k);
     for (uint32_t i = 0; i < k; ++i) {
         ioff[i] = o;
-        o = up256(o + jobs[i]->n + 64);   // + the staging loads' slack
+        o = up256(o + jobs[i]->st->n + 64);   // + the staging loads' slack
     }
     const size_t res_at = o;
     o = up256(res_at + 64ull * k);
     for (uint32_t i = 0; i < k; ++i) {
         ooff[i] = o;
-        o = up256(o + jobs[i]->cap);
+        o = up256(o + jobs[i]->st->cap);
     }
     const size_t total = o;
     if (!A.reserve(total)) return fail_all(jobs, A.hs);
     ZCall* zc = (ZCall*)A.h;
     for (uint32_t i = 0; i < k; ++i) {
-        const InflateJob* j = jobs[i];
-        if (j->n) std::memcpy(A.h + ioff[i], j->in, j->n);
+        const bpmd::InflateStep& s = *jobs[i]->st;
+        if (s.n) std::memcpy(A.h + ioff[i], s.in, s.n);
         ZCall c{};
-        c.st = j->s->zst;
+        c.st = jobs[i]->s->zst;
         c.in = A.d + ioff[i];
-        c.n_in = j->n;
+        c.n_in = s.n;
         c.out = A.d + ooff[i];
-        c.cap = j->cap;
+        c.cap = s.cap;
         c.res = A.d + res_at + 64ull * i;
-        c.flush = j->flush;
+        c.flush = s.flush;
         zc[i] = c;
     }
     const bool ok = hipMemcpyAsync(A.d, A.h, res_at, hipMemcpyHostToDevice, A.hs) == hipSuccess &&
                     bpmd_internal_zstream_write_batch(A.d, k, A.hs) == 0 &&
                     read_back(A, res_at, 64ull * k, total - res_at, ooff, [&](size_t i, size_t& len, size_t& room) {
-                        std::memcpy(&jobs[i]->res, A.h + res_at + 64ull * i, sizeof(Result));
-                        len = jobs[i]->res.out_used;
-                        room = jobs[i]->cap;
+                        bpmd::InflateStep& s = *jobs[i]->st;
+                        std::memcpy(&s.res, A.h + res_at + 64ull * i, sizeof(Result));
+                        len = s.res.out_used;
+                        room = s.cap;
                     });
     if (!ok) return fail_all(jobs, A.hs);
     for (uint32_t i = 0; i < k; ++i) {
-        InflateJob* j = jobs[i];
-        if (j->res.out_used) std::memcpy(j->out, A.h + ooff[i], j->res.out_used);
-        j->rc = BPMD_R_OK;
+        const bpmd::InflateStep& s = *jobs[i]->st;
+        if (s.res.out_used) std::memcpy(s.out, A.h + ooff[i], s.res.out_used);
+        jobs[i]->rc = BPMD_R_OK;
     }
 }
 
-// (a batch of one too: with the batcher on, streams use the leaders'
-// buffers and HIP stream and allocate none of their own -- creating a HIP
-// stream or pinned buffer per connection serializes in the runtime)
+// (a batch of one too.  With the batcher on, streams use the leaders' blocks
+// and HIP streams and allocate none of their own -- creating a HIP stream or
+// pinned buffer per connection serializes in the runtime; with it off a call
+// is inflate_batch of one on the stream's own arena, run_inflate)
 void inflate_exec(Arena& A, std::vector<InflateJob*>& jobs)
 {
     g_bstat[1].fetch_add(1);
@@ -592,50 +516,50 @@ void deflate_exec(Arena& A, std::vector<DeflateJob*>& jobs)
     }
 }
 
-// the inflate write()'s call, batched or not
-int inflate_call(Inflate* s, const uint8_t* in, size_t n, uint8_t* out, size_t cap, int flush, Result& res)
+// The call through its device's coalescer.  False with the batcher off (or
+// without a coalescer): the caller runs it alone, on the stream's own arena.
+template <class J, class Exec>
+bool batched(J& j, int stat, Exec&& exec)
 {
     const int mx = batch_max();
-    if (mx < 2) return inflate_one(s, in, n, out, cap, flush, res);
-    g_bstat[0].fetch_add(1);
+    if (mx < 2) return false;
+    g_bstat[stat].fetch_add(1);
+    int dev = 0;
+    Coalescer<J>* c = hipGetDevice(&dev) == hipSuccess ? coalescer<J>(dev) : nullptr;
+    if (!c) return false;
+    c->run(&j, mx, exec);
+    return true;
+}
+
+// the reader's device step (inflate_reader.h): the pending reset, then the
+// call through the coalescer, or as a batch of one
+int run_inflate(void* stream, bpmd::InflateStep& st)
+{
+    bpmd_stream* s = (bpmd_stream*)stream;
+    int r = bpmd_init();
+    if (r || (r = ensure_zhead(s, st)) != 0) return r;
     InflateJob j;
     j.s = s;
-    j.in = in;
-    j.n = n;
-    j.out = out;
-    j.cap = cap;
-    j.flush = flush;
-    int dev = 0;
-    Coalescer<InflateJob>* c = hipGetDevice(&dev) == hipSuccess ? coalescer<InflateJob>(dev) : nullptr;
-    if (!c) return inflate_one(s, in, n, out, cap, flush, res);
-    c->run(&j, mx, inflate_exec);
-    res = j.res;
+    j.st = &st;
+    if (batched(j, 0, inflate_exec)) return j.rc;
+    std::vector<InflateJob*> one{&j};
+    inflate_batch(s->arena, one);
     return j.rc;
 }
 
-// the writer's device step (deflate_writer.h): through the coalescer, or with
-// the batcher off as a group of one on the stream's own arena
+// the writer's device step (deflate_writer.h): through the coalescer, or as a
+// group of one
 int run_flush(void* stream, bpmd::DeflateStep& st)
 {
     bpmd_stream* s = (bpmd_stream*)stream;
     DeflateJob j;
     j.s = s;
     j.st = &st;
-    const int mx = batch_max();
-    Coalescer<DeflateJob>* c = nullptr;
-    if (mx >= 2) {
-        g_bstat[2].fetch_add(1);
-        int dev = 0;
-        if (hipGetDevice(&dev) == hipSuccess) c = coalescer<DeflateJob>(dev);
-    }
-    if (c) {
-        c->run(&j, mx, deflate_exec);
-        return j.rc;
-    }
+    if (batched(j, 2, deflate_exec)) return j.rc;
     const int r = bpmd_init();
     if (r) return r;
     std::vector<DeflateJob*> one{&j};
-    deflate_group(s->def.arena, one);
+    deflate_group(s->arena, one);
     return j.rc;
 }
 
@@ -665,76 +589,26 @@ extern "C" int bpmd_stream_batch_stats(unsigned long long* out, int reset)
     return BPMD_R_OK;
 }
 
-extern "C" int bpmd_inflate_stream_reset(bpmd_stream* s, int window_bits)
-{
-    if (!s || s->is_deflate) return BPMD_R_INVALID_ARGUMENT;
-    if (window_bits < 8 || window_bits > 15) return BPMD_R_DOMAIN_ERROR;
-    s->inf.wbits = window_bits;
-    s->inf.zreset = true;   // applied before the next write()
-    return BPMD_R_OK;
-}
-
-extern "C" int bpmd_inflate_stream_clear(bpmd_stream* s)
-{
-    // inflate_stream::clear -> doClear is empty in the reference
-    // (inflate_stream.ipp:49-53): state and window persist
-    return (!s || s->is_deflate) ? BPMD_R_INVALID_ARGUMENT : BPMD_R_OK;
-}
-
-extern "C" int bpmd_inflate_stream_write(bpmd_stream* s, bpmd_zparams* zs, int flush)
-{
-    if (!s || s->is_deflate || !zs || flush < BPMD_FLUSH_NONE || flush > BPMD_FLUSH_TREES)
-        return BPMD_R_INVALID_ARGUMENT;
-    if ((!zs->next_in && zs->avail_in) || (!zs->next_out && zs->avail_out)) return BPMD_STREAM_ERROR;
-    int r = bpmd_init();
-    if (r) return r;
-    const size_t n = zs->avail_in;
-    // Output room handed to the kernel.  A call cannot produce more than the
-    // pending match (<= 258) plus 258 bytes per 2 bits of the input and the
-    // reservoir (<= 32 bits), so a room of at least that plus 258 leaves the
-    // reference's "avail_out >= 258" fast-path test unchanged.
-    const size_t bound = 1040 * n + 8192;
-    const size_t cap = std::min<size_t>(zs->avail_out, bound);
-    if ((r = ensure_zhead(&s->inf)) != 0) return r;
-    Result res{};
-    if ((r = inflate_call(&s->inf, (const uint8_t*)zs->next_in, n, (uint8_t*)zs->next_out, cap, flush, res)) != 0)
-        return r;
-    if (res.published) {
-        zs->next_in = (const uint8_t*)zs->next_in + res.in_used;
-        zs->avail_in -= res.in_used;
-        zs->total_in += res.in_used;
-        zs->next_out = (uint8_t*)zs->next_out + res.out_used;
-        zs->avail_out -= res.out_used;
-        zs->total_out += res.out_used;
-        zs->data_type = res.data_type;
-    }
-    return res.ec;
-}
-
 extern "C" int bpmd_inflate_stream_footprint(const bpmd_stream* s, size_t* host_bytes, size_t* device_bytes)
 {
     if (!s || s->is_deflate) return BPMD_R_INVALID_ARGUMENT;
-    if (device_bytes)
-        *device_bytes = (s->inf.zst ? sizeof(State) + sizeof(Result) : 0) + s->inf.din_cap + s->inf.dout_cap;
-    if (host_bytes) *host_bytes = s->inf.hpin_cap;   // pinned staging only
+    // the state, and with the batcher off the stream's block and its pinned mirror
+    if (device_bytes) *device_bytes = (s->zst ? sizeof(State) + sizeof(Result) : 0) + s->arena.cap;
+    if (host_bytes) *host_bytes = s->arena.cap;
     return BPMD_R_OK;
 }
 
 extern "C" void bpmd_stream_destroy(bpmd_stream* s)
 {
     if (!s) return;
-    const Arena& A = s->def.arena;
-    const Inflate& I = s->inf;
-    for (hipStream_t hs : {A.hs, I.hs})
-        if (hs) (void)hipStreamSynchronize(hs);
-    for (void* p : {(void*)A.d, I.zst, (void*)I.din, (void*)I.dout})
+    const Arena& A = s->arena;
+    if (A.hs) (void)hipStreamSynchronize(A.hs);
+    for (void* p : {(void*)A.d, s->zst})
         if (p) (void)hipFree(p);
-    for (void* p : {(void*)A.h, (void*)I.hpin})
-        if (p) (void)hipHostFree(p);
-    for (hipStream_t hs : {A.hs, I.hs})
-        if (hs) {
-            bpmd_internal_scratch_release(hs);
-            (void)hipStreamDestroy(hs);
-        }
+    if (A.h) (void)hipHostFree(A.h);
+    if (A.hs) {
+        bpmd_internal_scratch_release(A.hs);
+        (void)hipStreamDestroy(A.hs);
+    }
     delete s;
 }

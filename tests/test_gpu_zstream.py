@@ -24,7 +24,9 @@ caller's buffer (tests/zstream_cases.py):
 * configs[0]'s shape (1 Ki x 1 KiB messages on one connection) with the
   stream's memory bounded.
 
-Every call here is a launch of its own.  The same checks on calls that share
+Every call here is a launch of its own, a batch of one on the batch leader's
+arena; test_both_transports and the tests after it also turn the batcher off,
+where the call is laid out on an arena the stream owns.  The same checks on calls that share
 a launch (the micro-batcher) are tests/test_gpu_stream_batch.py; that no call
 stores past its room or depends on the bytes after its input is
 tests/test_gpu_zstream_guard.py."""
@@ -45,6 +47,7 @@ def _lib():
     L.bpmd_inflate_stream_create.argtypes = [ctypes.c_int, ctypes.POINTER(vp)]
     L.bpmd_inflate_stream_write.argtypes = [vp, ctypes.POINTER(Z.ZParams), ctypes.c_int]
     L.bpmd_inflate_stream_reset.argtypes = [vp, ctypes.c_int]
+    L.bpmd_inflate_stream_clear.argtypes = [vp]
     L.bpmd_inflate_stream_footprint.argtypes = [vp, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t)]
     L.bpmd_stream_destroy.argtypes = [vp]
     return L
@@ -63,6 +66,9 @@ class GpuInflater:
 
     def reset(self, wbits):
         assert self.L.bpmd_inflate_stream_reset(self.h, wbits) == 0
+
+    def clear(self):
+        assert self.L.bpmd_inflate_stream_clear(self.h) == 0
 
     def footprint(self):
         hb, db = ctypes.c_size_t(), ctypes.c_size_t()
@@ -152,20 +158,76 @@ def test_serial_and_parallel_fast_loops(par):
 
 def test_reset_between_streams():
     """reset(windowBits) mid-stream: fresh state and window, new size."""
-    msgs = Z.msgs_of("json", [5000, 5000], seed=31)
-    s1 = Z.connection_stream(msgs[:1], level=6, mem=4)
-    s2 = Z.connection_stream(msgs[1:], level=6, wbits=10, mem=4)
-    g = GpuInflater(15)
-    o = Z.OracleInflater(15)
+    Z.case_reset_between_streams(make)
+
+
+def test_argument_checks():
+    Z.case_argument_checks(make)
+
+
+@pytest.fixture(params=[(0, 0), (256, 0)], ids=["unbatched", "batched"])
+def batching(request):
+    """The batcher off -- a call is a batch of one on the stream's own arena
+    -- and on: a lone call is a batch of one on the leader's."""
+    from tests.deflate_scripts import batching as setting
+    L = _lib()
+    before = setting(L)
+    assert L.bpmd_stream_batching(*request.param) == 0
     try:
-        Z.drive(g, s1, [(len(s1) // 2, 1 << 16, Z.SYNC)])
-        Z.drive(o, s1, [(len(s1) // 2, 1 << 16, Z.SYNC)])
-        g.reset(10)
-        o.z.reset(10)
-        calls = [(len(s2) // 3, 100, Z.SYNC), (len(s2), 1 << 16, Z.SYNC), (len(s2), 1 << 16, Z.SYNC)]
-        assert Z.drive(g, s2, calls) == Z.drive(o, s2, calls)
+        yield request.param
+    finally:
+        assert L.bpmd_stream_batching(*before) == 0
+
+
+BOTH = {
+    "kat_split": lambda: Z.case_kat_split(make, every_cut=False),
+    "errors": lambda: Z.case_errors(make),
+    "small_window": lambda: Z.case_small_window(make),
+    "stored_blocks": lambda: Z.case_stored_blocks(make),
+    "flush_mix": lambda: Z.case_flush_mix(make),
+    "end_of_stream": lambda: Z.case_end_of_stream(make),
+    "reset_between_streams": lambda: Z.case_reset_between_streams(make),
+    "argument_checks": lambda: Z.case_argument_checks(make),
+}
+
+
+@pytest.mark.parametrize("case", sorted(BOTH))
+def test_both_transports(batching, case):
+    """Call by call against the oracle, on every z_params field and byte, on
+    the stream's own arena and on a leader's."""
+    BOTH[case]()
+
+
+def test_output_over_four_mib_then_a_small_call(batching):
+    """One call whose room is over 4 MiB -- read_back brings the result
+    record first and then the used output, here with k = 1 -- and then a
+    small call of the same stream: the arena that grew is used again."""
+    Z.case_output_over_four_mib(make)
+
+
+def test_footprint_per_transport(batching):
+    """test_c1_connection_bounded_memory's connection, 128 messages long.
+    The batcher off: the stream holds its state and one arena with its pinned
+    mirror, neither growing with the connection's age.  On: the state alone
+    (less than any arena's 64 KiB), and nothing on the host."""
+    msgs = Z.msgs_of("json", [1024] * 128, seed=0x5EED0001)
+    pays = O.pmd_deflate_stream(msgs, 8, 15, 4)
+    g = GpuInflater(15)
+    a = Z.WsReader(g, 1536)
+    feet = []
+    try:
+        for i, p in enumerate(pays):
+            assert a.read_message([p], 4096) == (msgs[i], 0), i
+            if i in (15, 127):
+                feet.append(g.footprint())
     finally:
         g.close()
+    (h0, d0), (h1, d1) = feet
+    assert (h1, d1) == (h0, d0), feet
+    if batching[0] < 2:
+        assert 0 < h0 < 1 << 20 and h0 < d0 < 1 << 20, feet
+    else:
+        assert h0 == 0 and 0 < d0 < 1 << 16, feet
 
 
 def test_issue3028_one_byte_reads():

@@ -1,9 +1,9 @@
 """GPU: the per-stream inflate kernels inside their rooms.
 
 The host side copies back only a call's out_used bytes, so a store past
-out + cap never shows through the C ABI: in the single-call path it lands in
-slack, in the micro-batcher's arena (pmd_stream.hip inflate_batch, regions
-packed at 256-byte granularity) it lands in another connection's output.  The
+out + cap never shows through the C ABI: in the arena (pmd_stream.hip
+inflate_batch, regions packed at 256-byte granularity) it lands in padding
+or, in a batch of several, in another connection's output.  The
 kernel also reads its input 16 bytes at a time, up to 15 bytes past
 in + n_in; in the arena those bytes are left over from earlier batches.
 

@@ -1,8 +1,12 @@
 """CPU check of the per-stream inflate kernel's own logic
-(beast_amd/csrc/pmd_zstream.hip, zstream_run), compiled for the host by
-tests/model/zstream_host.py: every write()'s status, z_params and output
+(beast_amd/csrc/pmd_zstream.hip, zstream_run) and of the library's call
+protocol in front of it (beast_amd/csrc/inflate_reader.h), compiled for the
+host by tests/model/zstream_host.py: every write()'s status, z_params and output
 bytes must equal the oracle's restatement of Beast's inflate_stream.  The
 GPU build of the same code runs the same cases in tests/test_gpu_zstream.py."""
+import os
+import subprocess
+
 import pytest
 
 from tests import zstream_cases as Z
@@ -70,6 +74,30 @@ def test_stored_blocks():
 def test_errors():
     """(with the calls a connection makes after the error: BAD mode)"""
     Z.case_errors(make)
+
+
+def test_reset_between_streams():
+    Z.case_reset_between_streams(make)
+
+
+def test_argument_checks():
+    Z.case_argument_checks(make)
+
+
+def test_output_over_four_mib():
+    Z.case_output_over_four_mib(lambda w: H.GuardedHostInflater(w, 0xFF))
+
+
+def test_protocol_header_needs_no_hip():
+    """inflate_reader.h compiles with plain g++, warnings on, and includes beast_pmd.h, zstream.h and
+    the standard library only."""
+    header = os.path.join(H.CSRC, "inflate_reader.h")
+    r = subprocess.run(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-fsyntax-only", "-x", "c++", "-include",
+                        header, os.devnull], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    deps = subprocess.run(["g++", "-std=c++17", "-MM", "-x", "c++", header], capture_output=True, text=True, check=True)
+    names = {os.path.basename(p) for p in deps.stdout.replace("\\\n", " ").split()[1:]}
+    assert names == {"inflate_reader.h", "beast_pmd.h", "zstream.h"}, names
 
 
 @pytest.mark.parametrize("poison", [0x00, 0x5A, 0xFF])

@@ -10,7 +10,8 @@ Used by tests/test_gpu_zstream.py (the kernel, through the C ABI, a launch
 per call), tests/test_gpu_stream_batch.py (calls sharing a launch: plans of a
 fixed call count run in lockstep, run_lockstep), tests/test_gpu_zstream_guard.py
 (the kernels launched directly, inside guarded rooms) and
-tests/test_zstream_host.py (the kernel's own source built for the host)."""
+tests/test_zstream_host.py (the kernel's own source built for the host,
+behind the library's own call protocol)."""
 import ctypes
 import json
 import os
@@ -398,6 +399,112 @@ def case_errors(make):
         assert len(want) == len(calls) and calls_after(want, is_error) >= 1, trial
         after += calls_after(want, is_error)
     assert after >= 8   # calls made after an error were compared
+
+
+def case_reset_between_streams(make):
+    """reset(windowBits) mid-stream: fresh state and window, new size.  A
+    clear() in the middle of the second stream (doClear is empty,
+    inflate_stream.ipp:49-53) changes nothing in the calls that follow: the
+    oracle's side runs without it."""
+    msgs = msgs_of("json", [5000, 5000], seed=31)
+    s1 = connection_stream(msgs[:1], level=6, mem=4)
+    s2 = connection_stream(msgs[1:], level=6, wbits=10, mem=4)
+    g = make(15)
+    o = OracleInflater(15)
+    try:
+        drive(g, s1, [(len(s1) // 2, 1 << 16, SYNC)])
+        drive(o, s1, [(len(s1) // 2, 1 << 16, SYNC)])
+        g.reset(10)
+        o.z.reset(10)
+        calls = [(len(s2) // 3, 100, SYNC), (len(s2), 1 << 16, SYNC), (len(s2), 1 << 16, SYNC)]
+        writes = []
+
+        def clear_before_the_second():
+            writes.append(0)
+            if len(writes) == 2:
+                g.clear()
+
+        assert drive(g, s2, calls, before=clear_before_the_second) == drive(o, s2, calls)
+        assert len(writes) >= 2
+    finally:
+        g.close()
+
+
+def case_output_over_four_mib(make):
+    """5 MiB of zeros (about 5 KiB deflated) written in one call into a room
+    of 5 MiB + 4096, so the room handed to the decoder is over 4 MiB; then a
+    600-byte message of the same connection into a room of 1 KiB."""
+    msgs = [bytes(5 << 20), msgs_of("json", [600], seed=51)[0]]
+    pays = O.pmd_deflate_stream(msgs, 6, 15, 4)
+    stream = b"".join(p + EB for p in pays)
+    n, room = len(pays[0]) + 4, (5 << 20) + 4096
+    assert min(room, 1040 * n + 8192) > 4 << 20
+    want = compare(make, stream, [(n, room, SYNC), (len(stream), 1024, SYNC)], label="5 MiB of zeros")
+    assert [(r[0], r[1], r[3]) for r in want] == [(0, n, 5 << 20), (0, len(stream) - n, 600)]
+    assert want[0][8][:5 << 20] == msgs[0] and want[1][8][:600] == msgs[1]
+
+
+R_INVALID_ARGUMENT, R_DOMAIN_ERROR, STREAM_ERROR = -1, -2, 4   # include/beast_pmd.h
+
+
+def case_argument_checks(make):
+    """The call protocol's argument checks (beast_amd/csrc/inflate_reader.h),
+    through the C ABI of the inflater's library (inf.L, inf.h): windowBits 7
+    and 16 at create and at reset are BPMD_R_DOMAIN_ERROR, flush -1 and 7
+    BPMD_R_INVALID_ARGUMENT, a null next_in with avail_in 1 and a null
+    next_out with avail_out 1 BPMD_STREAM_ERROR.  Each refused write leaves
+    every z_params field as it was.  Each of them is made before every
+    write() of a stream -- on the fresh inflater and in mid-stream -- and
+    every write() still equals the oracle's, which never saw them: a known
+    answer, and a connection whose second message needs the first one's
+    window (a reset that took effect would lose it)."""
+    src = ctypes.create_string_buffer(b"\x00" * 16)
+    dst = ctypes.create_string_buffer(16)
+
+    def fields(zs):
+        return tuple(getattr(zs, f) for f, _ in ZParams._fields_)
+
+    def refused(inf, want, flush, next_in, avail_in, next_out, avail_out):
+        zs = ZParams(next_in, avail_in, 11, next_out, avail_out, 22, 12345)
+        was = fields(zs)
+        assert inf.L.bpmd_inflate_stream_write(inf.h, ctypes.byref(zs), flush) == want
+        assert fields(zs) == was and dst.raw == bytes(16)
+
+    def create(inf):
+        for w in (7, 16):
+            h = ctypes.c_void_p(1)
+            assert inf.L.bpmd_inflate_stream_create(w, ctypes.byref(h)) == R_DOMAIN_ERROR and not h.value
+
+    def reset(inf):
+        for w in (7, 16):
+            assert inf.L.bpmd_inflate_stream_reset(inf.h, w) == R_DOMAIN_ERROR
+
+    def flush(inf):
+        for fl in (-1, 7):
+            refused(inf, R_INVALID_ARGUMENT, fl, ctypes.addressof(src), 16, ctypes.addressof(dst), 16)
+
+    def null_in(inf):
+        refused(inf, STREAM_ERROR, SYNC, None, 1, ctypes.addressof(dst), 16)
+
+    def null_out(inf):
+        refused(inf, STREAM_ERROR, SYNC, ctypes.addressof(src), 16, None, 1)
+
+    kat = max((v for v in kat_vectors()["vectors"] if v["expect"] == "ok"), key=lambda v: len(v["in"]))
+    k = bytes.fromhex(kat["in"])
+    conn = connection_stream(msgs_of("json", [3000, 3000], seed=41), level=6, mem=4)
+    streams = [("kat", k, kat.get("wbits", 15), [(len(k) // 2, 1024, SYNC), (len(k), 1024, SYNC), (len(k), 1024, SYNC)]),
+               ("connection", conn, 15, [(len(conn) // 3, 1 << 16, SYNC), (2 * len(conn) // 3, 100, SYNC),
+                                         (len(conn), 1 << 16, SYNC), (len(conn), 1 << 16, SYNC)])]
+    for name, stream, wbits, calls in streams:
+        want = drive(OracleInflater(wbits), stream, calls)
+        assert len(want) == len(calls) and not any(is_error(r[0]) for r in want)
+        for bad in (create, reset, flush, null_in, null_out):
+            inf = make(wbits)
+            try:
+                got = drive(inf, stream, calls, before=lambda: bad(inf))
+            finally:
+                inf.close()
+            assert_records_equal(got, want, calls, label=f"{name} after {bad.__name__}")
 
 
 def failing_flips(good, rng, count, before=None):
