@@ -42,6 +42,7 @@
 
 #include "pmd_common.h"
 #include "canon.h"
+#include "hdr_list.h"
 #include "bp.h"
 #include "lane_io.h"
 #include "pmd_internal.h"
@@ -52,6 +53,8 @@ using namespace lio;
 
 // per-lane LDS layout (bytes)
 constexpr unsigned O_LIT = 0;      // u8[288]  literal/length symbols, canonical order (low 8 bits)
+                                   //          pass 1 -> pass 2: the list of coded runs (hdr_list.h), u16
+                                   //          entries growing down from byte 288
 constexpr unsigned O_DST = 288;    // u8[32]   distance symbols, canonical order
 constexpr unsigned O_HIST = 320;   // u32[16]  pass 1: length histogram (lit | lit<256 << 10 | dist << 20)
                                    //          pass 2: placement cursors (lit | dist << 16)
@@ -59,6 +62,7 @@ constexpr unsigned O_HIST = 320;   // u32[16]  pass 1: length histogram (lit | l
 constexpr unsigned O_LE = 384;     // u16[16]  litend per code length
 constexpr unsigned O_CLS = 416;    // u8[20]   code-length code symbols, canonical order  } data: token
 constexpr unsigned O_NIB = 448;    // u8[160]  code lengths, one nibble per symbol       } ring 8-31
+                                   //          pass 2 on the list path: u32[16] slots of the current runs
 constexpr unsigned O_HEAD = 624;   // u32      tokens written (decoder)
 constexpr unsigned O_TAIL = 628;   // u32      tokens taken (expander)
 constexpr unsigned STRIDE = 632;   // x 64 lanes x 4 workgroups = 161 792 B per CU
@@ -113,9 +117,16 @@ constexpr int KCL = BPMD3_KCL;   // code-length symbols per iteration (pass 1; a
 #ifndef BPMD3_KNIB
 #define BPMD3_KNIB 32
 #endif
-constexpr int KNIB = BPMD3_KNIB;  // code lengths placed per iteration (pass 2; a multiple of 8, at most 32)
+constexpr int KNIB = BPMD3_KNIB;  // code lengths placed per iteration (pass 2, nibble walk; a multiple of 8, at most 32)
+// BPMD3_PLIST=0: every header takes the nibble walk (the A/B arm of the list)
+#ifndef BPMD3_PLIST
+#define BPMD3_PLIST 1
+#endif
+constexpr uint32_t PL = 16;   // coded runs placed per iteration (pass 2, list walk)
+constexpr uint32_t DUMP = O_DST + 31;   // a byte no table uses (ndist <= 30): where a masked-off placement stores
+static_assert(hl::AREA == O_DST - O_LIT && hl::MAX_ENTRIES % PL == 0, "the run list lives in the literal/length symbol area");
 
-enum : uint32_t { S_TYPE, S_DATA, S_SHDR, S_SCOPY, S_DYN, S_PASS1, S_BUILD, S_PASS2, S_DONE };
+enum : uint32_t { S_TYPE, S_DATA, S_SHDR, S_SCOPY, S_DYN, S_PASS1, S_BUILD, S_PASS2, S_PLIST, S_DONE };
 
 __device__ __forceinline__ unsigned ring_at(uint32_t e)
 {
@@ -177,7 +188,8 @@ constexpr uint32_t W_HIST = O_HIST / 4, W_LE = O_LE / 4, W_NIB = O_NIB / 4, W_HE
 // header iterations [4] expander cycles [5] expander iterations [6] expander sleeps
 __device__ unsigned long long g_l3prof[16];
 // [0-4] decoder cycles in the header section's parts (type / stored / copy,
-// TABLE + LENLENS, CODELENS, BUILD, PLACE), [5-7] spare (prof build only)
+// TABLE + LENLENS, CODELENS, BUILD, PLACE), [5-7] per-task records; [7] bits
+// 40-63: lane-headers whose run list did not fit (prof build only)
 __device__ unsigned long long g_l3hprof[8];
 #ifdef BPMD_PROF
 #define L3_DECL unsigned long long l3t0_ = __builtin_amdgcn_s_memtime(), l3c_[4] = {0, 0, 0, 0}
@@ -816,6 +828,7 @@ __device__ __forceinline__ void decoder(uint8_t* T, bool valid, uint32_t m, cons
     Canon<7> tc;
     // header state
     uint32_t nlen = 0, ndist = 0, want = 0, have = 0, prev = 0;
+    uint32_t nent = 0;   // coded runs of this header (hdr_list.h)
     bool eob_seen = false, cl_empty = false;
     // stored block
     uint32_t srem = 0;
@@ -830,6 +843,7 @@ __device__ __forceinline__ void decoder(uint8_t* T, bool valid, uint32_t m, cons
     // decoder iterations, and 4-byte stored-copy steps -> g_l3hprof[5-7]
     unsigned long long tk_t0_ = 0;
     uint32_t tk_it_ = 0, tk_sc_ = 0;
+    unsigned long long l3fb_ = 0;   // lane-headers placed by the nibble walk (the list did not fit)
 #endif
     const uint32_t first_slots = s0 + gridDim.x * WG_MSGS;
     // the bit reader over payload bytes [p, p + n) (+ the pmd tail)
@@ -1380,6 +1394,7 @@ __device__ __forceinline__ void decoder(uint8_t* T, bool valid, uint32_t m, cons
                         for (int k = 0; k < 16; ++k) *lw(T, W_HIST + k) = 0u;
                         want = nlen + ndist;
                         have = 0;
+                        nent = 0;
                         prev = 0;
                         eob_seen = false;
                         st = S_PASS1;
@@ -1453,6 +1468,11 @@ __device__ __forceinline__ void decoder(uint8_t* T, bool valid, uint32_t m, cons
                             __hip_atomic_fetch_add(lw(T, W_HIST + val), nl | (nlo << 10) | (nd << 20), __ATOMIC_RELAXED,
                                                    __HIP_MEMORY_SCOPE_WORKGROUP);
                             if (a <= 256 && 256 < b) eob_seen = true;
+                            // the run's list entry (no return value; past the
+                            // area's capacity the header cannot fit anyway)
+                            if (BPMD3_PLIST && nent < hl::MAX_ENTRIES)
+                                *(uint16_t*)lb(T, O_LIT + hl::entry_off(nent)) = (uint16_t)hl::entry_pack(a, val, rep);
+                            ++nent;
                         }
                         prev = val;
                         have += rep;
@@ -1505,13 +1525,101 @@ __device__ __forceinline__ void decoder(uint8_t* T, bool valid, uint32_t m, cons
                         *lw(T, W_LE + (l >> 1)) = le0 | (le1 << 16);
                     }
                     have = 0;
-                    st = S_PASS2;
+                    // cl_: coded literal/length symbols.  The list path iff
+                    // its entries and the placed symbols cannot collide
+                    const bool fits = BPMD3_PLIST && hl::list_fits(nent, cl_);
+                    st = fits ? S_PLIST : S_PASS2;
+#ifdef BPMD_PROF
+                    l3fb_ += __builtin_popcountll(__ballot(!fits));
+#endif
                 }
             }
         }
         L3_HLAP(3);
-        if (st == S_PASS2) {
-            // place symbols in canonical order (inflate_stream.ipp:632-640)
+        // place symbols in canonical order (inflate_stream.ipp:632-640): the
+        // list walk over the coded runs, or, for a header whose list does
+        // not fit, the walk over every symbol's nibble.  Same placement
+        // either way; a wave issues only the forms some lane of it needs.
+        if (BPMD3_PLIST && __ballot(st == S_PLIST)) {
+            if (st == S_PLIST) {
+                // the lane's next PL entries, read before anything is placed;
+                // entry have + j is the high (j even) or low half of ew[7 - j / 2]
+                uint32_t ew[PL / 2];
+                const uint32_t wb = (O_LIT + hl::AREA) / 4 - have / 2 - PL / 2;
+                if (BPMD3_ILV) {
+#pragma unroll
+                    for (uint32_t k = 0; k < PL / 2; ++k) ew[k] = *lw(T, wb + k);
+                } else {
+#pragma unroll
+                    for (uint32_t k = 0; k < PL / 4; ++k) {
+                        const uint2 v = *(const uint2*)(T + 4 * wb + 8 * k);
+                        ew[2 * k] = v.x;
+                        ew[2 * k + 1] = v.y;
+                    }
+                }
+                const uint32_t cnt = nent - have;
+                uint32_t en[PL], olds[PL], multi = 0;
+                // one fetch-add per run (its symbols are consecutive and share
+                // a length, so they take consecutive slots); a run across nlen
+                // advances both cursors.  Entries past the list's end read as
+                // length 0: they move the unused cursor 0.
+#pragma unroll
+                for (uint32_t j = 0; j < PL; ++j) {
+                    const uint32_t w = ew[PL / 2 - 1 - j / 2];
+                    const uint32_t e = j < cnt ? ((j & 1) ? w & 0xffffu : w >> 16) : 0u;
+                    en[j] = e;
+                    multi |= e > 0x1fffu ? 1u << j : 0u;   // rep > 1
+                    const int32_t r = (int32_t)hl::entry_rep(e), d = (int32_t)nlen - (int32_t)hl::entry_first(e);
+                    const uint32_t nl = (uint32_t)(d < 0 ? 0 : d < r ? d : r);
+                    olds[j] = __hip_atomic_fetch_add(lw(T, W_HIST + hl::entry_len(e)), nl | (((uint32_t)r - nl) << 16),
+                                                     __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                }
+                // every run's first symbol: one byte store at a selected
+                // address, no branch (an entry of length 0 stores to DUMP)
+#pragma unroll
+                for (uint32_t j = 0; j < PL; ++j) {
+                    const uint32_t e = en[j], a = hl::entry_first(e);
+                    const bool lit = a < nlen;
+                    const uint32_t at = lit ? O_LIT + (olds[j] & 0xffffu) : O_DST + (olds[j] >> 16);
+                    *lb(T, hl::entry_len(e) ? at : DUMP) = (uint8_t)(lit ? a : a - nlen);
+                }
+                // The rest of the runs of a 16 repeat (few: deflated JSON has
+                // two or three per header), one run per lane and turn.  The
+                // slots go through the nibble array's LDS, which a header on
+                // the list path no longer needs, and the entry is read again
+                // from the list (placement never reaches it: the fit rule), so
+                // the turn indexes no register array.
+                if (__ballot(multi != 0)) {
+                    if (BPMD3_ILV) {
+#pragma unroll
+                        for (uint32_t j = 0; j < PL; ++j) *lw(T, W_NIB + j) = olds[j];
+                    } else {
+#pragma unroll
+                        for (uint32_t j = 0; j < PL; j += 2) *(uint2*)(T + O_NIB + 4 * j) = make_uint2(olds[j], olds[j + 1]);
+                    }
+                    while (__ballot(multi != 0)) {
+                        if (multi) {
+                            const uint32_t j = (uint32_t)__builtin_ctz(multi);
+                            multi &= multi - 1;
+                            const uint32_t e = *(const uint16_t*)lb(T, O_LIT + hl::entry_off(have + j));
+                            const uint32_t old = *lw(T, W_NIB + j);
+                            const uint32_t a = hl::entry_first(e), rep = hl::entry_rep(e);
+                            const int32_t d = (int32_t)nlen - (int32_t)a;
+                            const uint32_t nl = (uint32_t)(d < 0 ? 0 : d);   // symbols t >= d are distances
+#pragma unroll
+                            for (uint32_t t = 1; t < 6; ++t) {
+                                const bool lit = (int32_t)t < d;
+                                const uint32_t at = lit ? O_LIT + (old & 0xffffu) + t : O_DST + (old >> 16) + t - nl;
+                                *lb(T, t < rep ? at : DUMP) = (uint8_t)(lit ? a + t : a + t - nlen);
+                            }
+                        }
+                    }
+                }
+                have += PL;
+                if (have >= nent) st = S_DATA;
+            }
+        }
+        if (__ballot(st == S_PASS2) && st == S_PASS2) {
 #pragma unroll
             for (uint32_t h8 = 0; h8 < KNIB; h8 += 8) {
                 const uint32_t w = *lw(T, W_NIB + ((have + h8) >> 3));
@@ -1609,6 +1717,7 @@ __device__ __forceinline__ void decoder(uint8_t* T, bool valid, uint32_t m, cons
     {
         for (int i = 0; i < 4; ++i) atomicAdd(&g_l3prof[12 + i], l3x_[i]);
         atomicAdd(&g_l3prof[7], l3dyn_);
+        atomicAdd(&g_l3hprof[7], l3fb_ << 40);
     }
 #endif
 }

@@ -42,6 +42,9 @@ def main():
         if nm == "-":
             continue
         print(f"{nm:14s} {c[i] / w:12.0f} per wave")
+    # g_l3hprof[7]: bits 40-63 count the lane-headers whose run list did not
+    # fit and that took the walk over every symbol (hdr_list.h)
+    print(f"{'hdr: placed by the symbol walk':14s} {c[23] >> 40:12d} lane-headers")
     print("exact", ok)
 
 

@@ -67,7 +67,7 @@ def main():
         t5, t6 = r[21], r[22]
         print(f"{name}: longest task {t5 & 0x1ffff} (result {(t5 >> 17) & 0x7f}) {t5 >> 24} cycles; "
               f"most iterations task {t6 & 0x1ffff} (result {(t6 >> 17) & 0x7f}) {t6 >> 24}; "
-              f"stored-copy steps {r[23]}")
+              f"stored-copy steps {r[23] & ((1 << 40) - 1)}; headers placed by the symbol walk {r[23] >> 40}")
 
 
 if __name__ == "__main__":
