@@ -448,6 +448,28 @@ extern "C" int bpmd_frame_batch(const uint8_t* d_in, const uint64_t* d_in_off, c
                : BPMD_R_OK;
 }
 
+// read_some's frame loop over parse_fh (read.hpp:1063-1283, stream_impl.hpp:701-913)
+extern "C" int bpmd_unframe_batch(int role, int pmd_on, uint64_t msg_max, const uint8_t* d_wire,
+                                  const uint64_t* d_wire_off, const uint32_t* d_wire_len, uint32_t n,
+                                  bpmd_rd_state* d_state, uint8_t* d_out, const uint64_t* d_out_off,
+                                  const uint32_t* d_out_cap, uint32_t* d_out_len, uint8_t* d_op, uint8_t* d_compressed,
+                                  uint8_t* d_event, int32_t* d_status, uint32_t* d_consumed, uint8_t* d_ctl,
+                                  uint8_t* d_ctl_len, uint16_t* d_close_code, void* stream)
+{
+    if (role != BPMD_ROLE_SERVER && role != BPMD_ROLE_CLIENT) return BPMD_R_INVALID_ARGUMENT;
+    if (n == 0) return BPMD_R_OK;
+    if (!d_wire || !d_wire_off || !d_wire_len || !d_out || !d_out_off || !d_out_cap || !d_out_len || !d_op ||
+        !d_compressed || !d_event || !d_status || !d_consumed || !d_ctl || !d_ctl_len || !d_close_code)
+        return BPMD_R_INVALID_ARGUMENT;
+    int r = bpmd_init();
+    if (r) return r;
+    return launch_unframe((uint32_t)role, pmd_on ? 1u : 0u, msg_max, d_wire, d_wire_off, d_wire_len, n, d_state, d_out,
+                          d_out_off, d_out_cap, d_out_len, d_op, d_compressed, d_event, d_status, d_consumed, d_ctl,
+                          d_ctl_len, d_close_code, (hipStream_t)stream)
+               ? BPMD_R_HIP_ERROR
+               : BPMD_R_OK;
+}
+
 extern "C" int bpmd_utf8_check_batch(const uint8_t* d_data, const uint64_t* d_off, const uint32_t* d_len,
                                      uint32_t n_msgs, int32_t* d_result, void* stream)
 {

@@ -26,6 +26,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/beast_pmd.h"
+#include "frame_parse.h"
 #include "pmd_internal.h"
 
 namespace bpmd {
@@ -232,6 +234,24 @@ __device__ __forceinline__ uint32_t hdr_len(uint64_t len, bool masked)
 
 typedef uint4 uint4_fu __attribute__((aligned(1)));
 
+// One frame's payload, XORed with the frame's key on the way (masking is an
+// involution): 16 bytes per lane per step at frame offsets that are multiples
+// of 16, so every dword takes the key as it is, then a byte tail.
+__device__ __forceinline__ void copy_xor(uint8_t* dst, const uint8_t* src, uint32_t len, uint32_t key, unsigned lane)
+{
+    const uint32_t full = len >> 4;
+    for (uint32_t u = lane; u < full; u += WAVE) {
+        uint4 v = *(const uint4_fu*)(src + 16 * u);
+        v.x ^= key;
+        v.y ^= key;
+        v.z ^= key;
+        v.w ^= key;
+        *(uint4_fu*)(dst + 16 * u) = v;
+    }
+    const uint32_t t = 16 * full + lane;
+    if (t < len) dst[t] = src[t] ^ (uint8_t)(key >> (8 * (t & 3u)));
+}
+
 __global__ void __launch_bounds__(WAVE * WPB)
 frame_kernel(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_off, const uint32_t* __restrict__ in_len,
              const uint8_t* __restrict__ op, const uint8_t* __restrict__ flags, const uint32_t* __restrict__ keys,
@@ -276,23 +296,88 @@ frame_kernel(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_off
                 hl += 4;
             }
             if (lane < hl) w[wp + lane] = (uint8_t)((lane < 8 ? h0 >> (8 * lane) : h1 >> (8 * (lane - 8))) & 0xffu);
-            uint8_t* dst = w + wp + hl;
-            const uint8_t* src = p + a;
-            const uint32_t full = len >> 4;
-            for (uint32_t u = lane; u < full; u += WAVE) {
-                uint4 v = *(const uint4_fu*)(src + 16 * u);
-                v.x ^= key;
-                v.y ^= key;
-                v.z ^= key;
-                v.w ^= key;
-                *(uint4_fu*)(dst + 16 * u) = v;
-            }
-            const uint32_t t = 16 * full + lane;
-            if (t < len) dst[t] = src[t] ^ (uint8_t)(key >> (8 * (t & 3u)));
+            copy_xor(w + wp + hl, p + a, len, key, lane);
             wp += hl + len;
         }
     }
 }
+
+// Receive side, frame_kernel's mirror (read.hpp:1063-1283 read_some's frame
+// loop over parse_fh, stream_impl.hpp:701-913): one wave per entry walks the
+// frames in the entry's wire bytes.  The walk is wave-uniform: every lane
+// runs the header step (frame_parse.h) on the same bytes, which are loaded
+// only below the entry's wire_len.  A data frame's payload is unmasked with
+// the frame's own key and appended to the entry's out slot, 16 bytes per lane
+// per step at frame offsets that are multiples of 16 (so every dword takes
+// the key as it is), then a byte tail; a control frame's payload goes to the
+// entry's 128-byte control slot.  The walk stops at the first complete
+// message, control frame, refused header or end of the buffer.
+//
+// Whole frames only: a frame whose header or payload the buffer cuts is left
+// unconsumed, where Beast consumes the part of a data frame's payload that
+// has arrived (rd_remain, read.hpp:1201-1280); the caller keeps those bytes and
+// calls again once more have come.  The wire is only read; stores stay inside
+// [out_off, out_off + out_cap), which the header step's buffer_overflow check
+// guarantees before any byte of a frame is copied.
+__global__ void __launch_bounds__(WAVE * WPB)
+unframe_kernel(uint32_t role, uint32_t pmd_on, uint64_t msg_max, const uint8_t* __restrict__ wire,
+               const uint64_t* __restrict__ wire_off, const uint32_t* __restrict__ wire_len, uint32_t n,
+               fp::RdState* __restrict__ state, uint8_t* __restrict__ out, const uint64_t* __restrict__ out_off,
+               const uint32_t* __restrict__ out_cap, uint32_t* __restrict__ out_len, uint8_t* __restrict__ op,
+               uint8_t* __restrict__ compressed, uint8_t* __restrict__ event, int32_t* __restrict__ status,
+               uint32_t* __restrict__ consumed, uint8_t* __restrict__ ctl, uint8_t* __restrict__ ctl_len,
+               uint16_t* __restrict__ close_code)
+{
+    const unsigned lane = threadIdx.x & (WAVE - 1);
+    for (uint32_t m = blockIdx.x * WPB + (threadIdx.x / WAVE); m < n; m += gridDim.x * WPB) {
+        const uint8_t* p = wire + wire_off[m];
+        const uint32_t wl = wire_len[m], cap = out_cap[m];
+        uint8_t* dst = out + out_off[m];
+        fp::RdState st;
+        if (state) st = state[m];
+        else fp::reset(st);
+        uint8_t* c = ctl + 128u * (uint64_t)m;
+        fp::Stop s;
+        fp::walk(
+            p, wl, role, pmd_on != 0, msg_max, cap, st,
+            [&](uint64_t at, const uint8_t* src, uint32_t len, uint32_t key) {
+                copy_xor(dst + at, src, len, key, lane);
+            },
+            [&](const uint8_t* src, uint32_t len, uint32_t key) {
+                for (uint32_t t = lane; t < len; t += WAVE) c[t] = src[t] ^ (uint8_t)(key >> (8 * (t & 3u)));
+            },
+            s);
+        if (lane == 0) {
+            out_len[m] = (uint32_t)s.msg_len;
+            op[m] = (uint8_t)s.msg_op;
+            compressed[m] = (uint8_t)s.msg_deflated;
+            event[m] = (uint8_t)s.event;
+            status[m] = s.status;
+            consumed[m] = s.consumed;
+            ctl_len[m] = (uint8_t)s.ctl_len;
+            close_code[m] = s.close_code;
+            if (state) state[m] = st;
+        }
+    }
+}
+
+// frame_parse.h names its outcomes without the public header
+static_assert(fp::E_BAD_FRAME_PAYLOAD == BPMD_BAD_FRAME_PAYLOAD && fp::E_BUFFER_OVERFLOW == BPMD_WS_BUFFER_OVERFLOW &&
+                  fp::E_MESSAGE_TOO_BIG == BPMD_WS_MESSAGE_TOO_BIG && fp::E_BAD_OPCODE == BPMD_WS_BAD_OPCODE &&
+                  fp::E_BAD_DATA_FRAME == BPMD_WS_BAD_DATA_FRAME && fp::E_BAD_CONTINUATION == BPMD_WS_BAD_CONTINUATION &&
+                  fp::E_BAD_RESERVED_BITS == BPMD_WS_BAD_RESERVED_BITS &&
+                  fp::E_BAD_CONTROL_FRAGMENT == BPMD_WS_BAD_CONTROL_FRAGMENT &&
+                  fp::E_BAD_CONTROL_SIZE == BPMD_WS_BAD_CONTROL_SIZE &&
+                  fp::E_BAD_UNMASKED_FRAME == BPMD_WS_BAD_UNMASKED_FRAME &&
+                  fp::E_BAD_MASKED_FRAME == BPMD_WS_BAD_MASKED_FRAME && fp::E_BAD_SIZE == BPMD_WS_BAD_SIZE &&
+                  fp::E_BAD_CLOSE_CODE == BPMD_WS_BAD_CLOSE_CODE && fp::E_BAD_CLOSE_SIZE == BPMD_WS_BAD_CLOSE_SIZE &&
+                  fp::E_BAD_CLOSE_PAYLOAD == BPMD_WS_BAD_CLOSE_PAYLOAD,
+              "frame_parse.h and beast_pmd.h name the same websocket::error values");
+static_assert(sizeof(fp::RdState) == sizeof(bpmd_rd_state), "bpmd_rd_state is RdState");
+static_assert(fp::EV_NEED_MORE == BPMD_EV_NEED_MORE && fp::EV_MESSAGE == BPMD_EV_MESSAGE && fp::EV_PING == BPMD_EV_PING &&
+                  fp::EV_PONG == BPMD_EV_PONG && fp::EV_CLOSE == BPMD_EV_CLOSE &&
+                  fp::ROLE_SERVER == BPMD_ROLE_SERVER && fp::ROLE_CLIENT == BPMD_ROLE_CLIENT,
+              "frame_parse.h and beast_pmd.h name the same events and roles");
 
 }  // namespace frame
 }  // namespace bpmd
@@ -339,5 +424,18 @@ int bpmd::launch_frame(const uint8_t* in, const uint64_t* in_off, const uint32_t
     if (n == 0) return 0;
     hipLaunchKernelGGL(bpmd::frame::frame_kernel, dim3(frame_grid(n)), dim3(bpmd::frame::WAVE * bpmd::frame::WPB), 0,
                        stream, in, in_off, in_len, op, flags, keys, key_base, frame_max, n, wire, wire_off);
+    return (int)hipGetLastError();
+}
+
+int bpmd::launch_unframe(uint32_t role, uint32_t pmd_on, uint64_t msg_max, const uint8_t* wire, const uint64_t* wire_off,
+                         const uint32_t* wire_len, uint32_t n, void* state, uint8_t* out, const uint64_t* out_off,
+                         const uint32_t* out_cap, uint32_t* out_len, uint8_t* op, uint8_t* compressed, uint8_t* event,
+                         int32_t* status, uint32_t* consumed, uint8_t* ctl, uint8_t* ctl_len, uint16_t* close_code,
+                         hipStream_t stream)
+{
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(bpmd::frame::unframe_kernel, dim3(frame_grid(n)), dim3(bpmd::frame::WAVE * bpmd::frame::WPB), 0,
+                       stream, role, pmd_on, msg_max, wire, wire_off, wire_len, n, (bpmd::fp::RdState*)state, out,
+                       out_off, out_cap, out_len, op, compressed, event, status, consumed, ctl, ctl_len, close_code);
     return (int)hipGetLastError();
 }

@@ -123,6 +123,12 @@ int launch_slide(uint8_t* buf, const uint64_t* base, const uint32_t* pos, const 
 int launch_frame(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, const uint8_t* op,
                  const uint8_t* flags, const uint32_t* keys, const uint32_t* key_base, uint32_t frame_max, uint32_t n,
                  uint8_t* wire, const uint64_t* wire_off, hipStream_t stream);
+// state: bpmd_rd_state per entry (frame_parse.h RdState), or NULL
+int launch_unframe(uint32_t role, uint32_t pmd_on, uint64_t msg_max, const uint8_t* wire, const uint64_t* wire_off,
+                   const uint32_t* wire_len, uint32_t n, void* state, uint8_t* out, const uint64_t* out_off,
+                   const uint32_t* out_cap, uint32_t* out_len, uint8_t* op, uint8_t* compressed, uint8_t* event,
+                   int32_t* status, uint32_t* consumed, uint8_t* ctl, uint8_t* ctl_len, uint16_t* close_code,
+                   hipStream_t stream);
 
 }  // namespace bpmd
 

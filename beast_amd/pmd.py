@@ -12,6 +12,7 @@ Batch layout (struct of arrays, all device tensors):
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
 from dataclasses import dataclass
@@ -75,6 +76,8 @@ def lib():
         L.bpmd_frame_wire_size.argtypes = [ctypes.c_uint64, u32, ctypes.c_int]
         L.bpmd_frame_wire_size.restype = ctypes.c_uint64
         L.bpmd_frame_batch.argtypes = [vp, vp, vp, vp, vp, vp, vp, u32, u32, vp, vp, vp]
+        L.bpmd_unframe_batch.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint64, vp, vp, vp, u32] + [vp] * 14
+        L.bpmd_unframe_batch.restype = ctypes.c_int
         L.bpmd_read_batch.argtypes = [ctypes.POINTER(_Cfg), vp, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp]
         L.bpmd_write_batch.argtypes = [ctypes.POINTER(_Cfg), vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp]
         L.bpmd_inflate_takeover_batch.argtypes = [ctypes.POINTER(_Cfg), vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp]
@@ -108,6 +111,11 @@ def _stream_handle(stream):
     if stream is None:
         stream = torch.cuda.current_stream()
     return ctypes.c_void_p(stream.cuda_stream)
+
+
+def _on(stream):
+    """torch work that follows a launch on `stream` runs on it too"""
+    return contextlib.nullcontext() if stream is None else torch.cuda.stream(stream)
 
 
 def upper_bound(n: int) -> int:
@@ -419,6 +427,131 @@ def write_batch(src: Batch, key=None, level: int = 6, window_bits: int = 15, mem
                               _ptr(out), _ptr(out_off), _ptr(cap), _ptr(out_len), _ptr(status),
                               _stream_handle(stream)), "bpmd_write_batch")
     return Result(Batch(out, out_off, out_len), cap, status)
+
+
+# ------------------------------------------------------------------------
+# Receive side: wire bytes -> frames -> messages (bpmd_unframe_batch)
+
+ROLE_SERVER, ROLE_CLIENT = 0, 1
+# bpmd_event: what stopped an entry's walk
+EV_NEED_MORE, EV_MESSAGE, EV_PING, EV_PONG, EV_CLOSE = 0, 1, 2, 3, 4
+# bpmd_ws_error: websocket::error values of the status array (websocket/error.hpp)
+WS_ERRORS = {256: "bad_frame_payload", 257: "buffer_overflow", 258: "message_too_big", 259: "bad_opcode",
+             260: "bad_data_frame", 261: "bad_continuation", 262: "bad_reserved_bits", 263: "bad_control_fragment",
+             264: "bad_control_size", 265: "bad_unmasked_frame", 266: "bad_masked_frame", 267: "bad_size",
+             268: "bad_close_code", 269: "bad_close_size", 270: "bad_close_payload"}
+(WS_BUFFER_OVERFLOW, WS_MESSAGE_TOO_BIG, WS_BAD_OPCODE, WS_BAD_DATA_FRAME, WS_BAD_CONTINUATION, WS_BAD_RESERVED_BITS,
+ WS_BAD_CONTROL_FRAGMENT, WS_BAD_CONTROL_SIZE, WS_BAD_UNMASKED_FRAME, WS_BAD_MASKED_FRAME, WS_BAD_SIZE,
+ WS_BAD_CLOSE_CODE, WS_BAD_CLOSE_SIZE, WS_BAD_CLOSE_PAYLOAD) = range(257, 271)
+CTL_SLOT = 128        # bytes of an entry's control payload slot
+RD_STATE_BYTES = 16   # sizeof(bpmd_rd_state)
+
+
+def rd_state(n: int, device="cuda") -> torch.Tensor:
+    """n bpmd_rd_state records, all between messages (uint8 [n, 16]: rd_size
+    little-endian in bytes 0-7, then rd_cont, rd_op, rd_deflated)."""
+    return torch.zeros((n, RD_STATE_BYTES), dtype=torch.uint8, device=device)
+
+
+@dataclass
+class Unframed:
+    out: Batch                 # gathered payloads: out.len = bytes of the message (complete or in progress)
+    cap: torch.Tensor          # int32 slot capacities
+    op: torch.Tensor           # uint8: 1 text, 2 binary
+    compressed: torch.Tensor   # uint8: the message's RSV1
+    event: torch.Tensor        # uint8 EV_*
+    status: torch.Tensor       # int32: 0 or a WS_* error
+    consumed: torch.Tensor     # int32 wire bytes consumed
+    ctl: torch.Tensor          # uint8 [n, 128] control payloads
+    ctl_len: torch.Tensor      # uint8
+    close_code: torch.Tensor   # int32 (0 = none)
+    state: torch.Tensor | None  # uint8 [n, 16], the caller's, updated in place
+
+
+def unframe_batch(wire: Batch, out_cap, role: int, pmd_on: bool = True, msg_max: int = 16 << 20,
+                  state: torch.Tensor | None = None, out: torch.Tensor | None = None,
+                  out_off: torch.Tensor | None = None, stream=None) -> Unframed:
+    """bpmd_unframe_batch: walk the frames of every entry of `wire` as
+    read_some does around parse_fh (read.hpp:1063-1283, stream_impl.hpp:
+    701-913), unmask data payloads into the entry's out slot and stop at the
+    first complete message, control frame, refused header or end of buffer
+    (include/beast_pmd.h).  Whole frames only: drop `consumed` bytes of each
+    entry, keep the rest and call again with the same `state` (rd_state) and
+    out slots; `state` None starts every entry between messages."""
+    L = lib()
+    dev = wire.data.device
+    n = wire.n
+    cap, out, out_off = _out_slots(n, dev, out_cap, out, out_off)
+    if state is not None and (state.dtype != torch.uint8 or state.numel() != n * RD_STATE_BYTES
+                              or not state.is_contiguous()):
+        raise BpmdError("unframe_batch: state must be rd_state(n)")
+    out_len = torch.empty(n, dtype=torch.int32, device=dev)
+    u8 = lambda *shape: torch.empty(shape, dtype=torch.uint8, device=dev)  # noqa: E731
+    op, comp, event, ctl_len, ctl = u8(n), u8(n), u8(n), u8(n), u8(n, CTL_SLOT)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    consumed = torch.empty(n, dtype=torch.int32, device=dev)
+    code = torch.empty(n, dtype=torch.int16, device=dev)
+    _check(L.bpmd_unframe_batch(role, 1 if pmd_on else 0, msg_max, _ptr(wire.data), _ptr(wire.off), _ptr(wire.len), n,
+                                _optr(state), _ptr(out), _ptr(out_off), _ptr(cap), _ptr(out_len), _ptr(op),
+                                _ptr(comp), _ptr(event), _ptr(status), _ptr(consumed), _ptr(ctl), _ptr(ctl_len),
+                                _ptr(code), _stream_handle(stream)), "bpmd_unframe_batch")
+    with _on(stream):
+        code = code.to(torch.int32) & 0xFFFF
+    return Unframed(Batch(out, out_off, out_len), cap, op, comp, event, status, consumed, ctl, ctl_len, code, state)
+
+
+@dataclass
+class Received:
+    frames: Unframed            # the frame pass's results, entry by entry
+    event: torch.Tensor         # uint8 EV_* (frames.event)
+    status: torch.Tensor        # int32: the frame status, else the message's read_batch status
+    inflated: Result | None     # read_batch over the entries in `inflated_idx`
+    inflated_idx: torch.Tensor  # int64: entries that completed a compressed message
+
+    def to_host(self):
+        """Per entry: the message's bytes after EV_MESSAGE (inflated if it was
+        compressed), else None."""
+        ev = self.event.cpu().tolist()
+        plain = self.frames.out
+        msgs = [plain.message(i) if e == EV_MESSAGE else None for i, e in enumerate(ev)]
+        for j, i in enumerate(self.inflated_idx.cpu().tolist()):
+            msgs[i] = self.inflated.out.message(j)
+        return msgs
+
+
+def receive_batch(wire: Batch, out_cap, inflate_cap, role: int, pmd_on: bool = True, msg_max: int = 16 << 20,
+                  state: torch.Tensor | None = None, out: torch.Tensor | None = None,
+                  out_off: torch.Tensor | None = None, window_bits: int = 15, stream=None) -> Received:
+    """From wire bytes to messages (read.hpp:1063-1385): unframe_batch, then
+    read_batch (inflate + UTF-8 check of text) over the entries that completed
+    a compressed message -- a batch over the same out buffer with the gathered
+    offsets and lengths, `inflate_cap` output bytes each (Beast checks
+    rd_msg_max while inflating, read.hpp:1357-1366; here need_buffers says the
+    message outgrew inflate_cap) -- and utf8_check_batch over the complete
+    uncompressed text messages, which keep their gathered payload.  A text
+    message that is not UTF-8 gets BAD_FRAME_PAYLOAD.  Picking the entries
+    waits for the frame pass."""
+    with _on(stream):
+        return _receive(wire, out_cap, inflate_cap, role, pmd_on, msg_max, state, out, out_off, window_bits, stream)
+
+
+def _receive(wire, out_cap, inflate_cap, role, pmd_on, msg_max, state, out, out_off, window_bits, stream):
+    u = unframe_batch(wire, out_cap, role, pmd_on, msg_max, state, out, out_off, stream)
+    status = u.status.clone()
+    done = (u.event == EV_MESSAGE) & (u.status == 0)
+    zi = torch.nonzero(done & (u.compressed != 0)).flatten()
+    ti = torch.nonzero(done & (u.compressed == 0) & (u.op == 1)).flatten()
+    inflated = None
+    if zi.numel():
+        sub = Batch(u.out.data, u.out.off[zi].contiguous(), u.out.len[zi].contiguous())
+        icap = inflate_cap if isinstance(inflate_cap, int) else inflate_cap.to(u.out.data.device)[zi].contiguous()
+        inflated = read_batch(sub, icap, key=None, text=(u.op[zi] == 1), window_bits=window_bits, stream=stream)
+        status[zi] = inflated.status
+    if ti.numel():
+        sub = Batch(u.out.data, u.out.off[ti].contiguous(), u.out.len[ti].contiguous())
+        verdict = utf8_check_batch(sub, stream=stream)
+        status[ti] = torch.where(verdict != 0, BAD_FRAME_PAYLOAD, 0).to(torch.int32)
+    return Received(u, u.event, status, inflated, zi)
 
 
 # ------------------------------------------------------------------------

@@ -272,6 +272,110 @@ int bpmd_frame_batch(const uint8_t* d_in, const uint64_t* d_in_off, const uint32
                      uint32_t n_msgs, uint8_t* d_wire, const uint64_t* d_wire_off, void* stream);
 
 /* ---------------------------------------------------------------------
+ * Receive side: from wire bytes to message payloads.  What read_some does
+ * per connection (websocket/impl/read.hpp:1063-1283) around parse_fh
+ * (websocket/impl/stream_impl.hpp:701-913), over a batch of connections.
+ * ------------------------------------------------------------------- */
+
+/* The message state parse_fh keeps between frames (stream_impl.hpp:78-87
+ * rd_size, rd_op, rd_cont; impl_base.hpp:61-78 rd_set), one per entry.  All
+ * zero = between messages. */
+typedef struct bpmd_rd_state {
+    uint64_t rd_size;    /* payload bytes of the current message gathered so far */
+    uint8_t rd_cont;     /* a continuation frame is expected */
+    uint8_t rd_op;       /* opcode of the current message: 1 text, 2 binary */
+    uint8_t rd_deflated; /* the current message's first frame had RSV1 */
+    uint8_t reserved[5]; /* zero */
+} bpmd_rd_state;
+
+/* role_type (websocket/rfc6455.hpp) of the reading end */
+enum bpmd_role {
+    BPMD_ROLE_SERVER = 0, /* frames must be masked (stream_impl.hpp:805-810) */
+    BPMD_ROLE_CLIENT = 1  /* frames must not be masked (stream_impl.hpp:811-816) */
+};
+
+/* What stopped an entry's walk (d_event) */
+enum bpmd_event {
+    BPMD_EV_NEED_MORE = 0, /* the buffer ended, or d_status[i] holds a parse error */
+    BPMD_EV_MESSAGE = 1,   /* a FIN data frame: the message is complete (read.hpp:1281-1283) */
+    BPMD_EV_PING = 2,      /* read.hpp:1130-1150 */
+    BPMD_EV_PONG = 3,      /* read.hpp:1151-1160 */
+    BPMD_EV_CLOSE = 4      /* read.hpp:1161-1199 */
+};
+
+/* websocket::error (websocket/error.hpp:22-226) values of d_status, beside
+ * BPMD_BAD_FRAME_PAYLOAD; all above every zlib::error value. */
+enum bpmd_ws_error {
+    BPMD_WS_BUFFER_OVERFLOW = 257,      /* error::buffer_overflow: the message does not fit d_out_cap[i] */
+    BPMD_WS_MESSAGE_TOO_BIG = 258,      /* error::message_too_big (stream_impl.hpp:886-906) */
+    BPMD_WS_BAD_OPCODE = 259,           /* error::bad_opcode (:779-784) */
+    BPMD_WS_BAD_DATA_FRAME = 260,       /* error::bad_data_frame (:748-753) */
+    BPMD_WS_BAD_CONTINUATION = 261,     /* error::bad_continuation (:764-769) */
+    BPMD_WS_BAD_RESERVED_BITS = 262,    /* error::bad_reserved_bits (:754-760, :770-775, :797-802) */
+    BPMD_WS_BAD_CONTROL_FRAGMENT = 263, /* error::bad_control_fragment (:785-790) */
+    BPMD_WS_BAD_CONTROL_SIZE = 264,     /* error::bad_control_size (:791-796) */
+    BPMD_WS_BAD_UNMASKED_FRAME = 265,   /* error::bad_unmasked_frame (:805-810) */
+    BPMD_WS_BAD_MASKED_FRAME = 266,     /* error::bad_masked_frame (:811-816) */
+    BPMD_WS_BAD_SIZE = 267,             /* error::bad_size (:833-838, :848-859) */
+    BPMD_WS_BAD_CLOSE_CODE = 268,       /* error::bad_close_code (frame.hpp:225-230) */
+    BPMD_WS_BAD_CLOSE_SIZE = 269,       /* error::bad_close_size (frame.hpp:209-214) */
+    BPMD_WS_BAD_CLOSE_PAYLOAD = 270     /* error::bad_close_payload (frame.hpp:232-238) */
+};
+
+/* Frames of a batch of connections on the receive side (replaces the
+ * parse_fh loop of read_some, read.hpp:1085-1283, with detail::read_ping,
+ * read_close and is_valid_close_code, websocket/detail/frame.hpp:94-126,
+ * 181-240; bpmd_frame_batch's inverse).  Entry i holds d_wire_len[i] bytes
+ * at d_wire + d_wire_off[i], read in `role`; pmd_on != 0 means
+ * permessage-deflate was negotiated, so RSV1 is legal on a message's first
+ * frame (impl_base.hpp:61-78; :381-390 without it); msg_max is rd_msg_max
+ * (0 = no limit), applied to uncompressed messages at header time as
+ * stream_impl.hpp:894-906 does.
+ *
+ * The entry's frames are walked from the start.  A data frame's payload is
+ * unmasked with the frame's key and appended to the out slot at
+ * d_out + d_out_off[i] + rd_size.  The walk stops at the first of:
+ *   BPMD_EV_MESSAGE  a FIN data frame was consumed: d_out_len[i] is the
+ *       message's payload length, d_op[i] its opcode (1 text, 2 binary),
+ *       d_compressed[i] its RSV1; the state is reset.
+ *   BPMD_EV_PING / _PONG / _CLOSE  a control frame was consumed (it may
+ *       come between a message's fragments; those before it are appended
+ *       and the state is kept): its unmasked payload is at d_ctl + 128 * i,
+ *       d_ctl_len[i] bytes.  For a close, d_close_code[i] is the code (0 for
+ *       an empty payload) and d_status[i] is 0 or bad_close_size /
+ *       bad_close_code / bad_close_payload as read_close decides; the frame
+ *       counts as consumed either way, as in Beast.
+ *   BPMD_EV_NEED_MORE  the buffer ended, or a header was refused and
+ *       d_status[i] holds the parse_fh error; the refused frame is not
+ *       consumed and the frames before it keep their effect.
+ * Except after BPMD_EV_MESSAGE, d_out_len / d_op / d_compressed describe
+ * the message in progress (zero between messages).  d_consumed[i] is the
+ * number of wire bytes consumed; the caller drops them, keeps the rest and
+ * calls again, with more bytes after NEED_MORE.  d_state carries each
+ * entry's message state from call to call, together with the gathered bytes
+ * in its out slot; NULL = every entry starts between messages and no state
+ * is stored.
+ *
+ * One deliberate difference from Beast: only whole frames are consumed.  A
+ * frame whose header or payload the buffer cuts stays unconsumed, where
+ * Beast hands over the part of a data frame's payload that has arrived
+ * (rd_remain, read.hpp:1201-1280).  So that a frame which can never fit is
+ * refused at once, not waited for, a data frame whose rd_size + length
+ * exceeds d_out_cap[i] is refused at header time with buffer_overflow, after
+ * parse_fh's own checks.
+ *
+ * d_wire is not modified and must not overlap d_out; no byte outside
+ * [d_out_off[i], d_out_off[i] + d_out_cap[i]) is written, and none beyond
+ * the gathered length.  Asynchronous on `stream`.  n == 0 is a no-op;
+ * BPMD_R_INVALID_ARGUMENT for a role that is neither, or for a NULL pointer
+ * other than d_state; BPMD_R_NO_DEVICE without a GPU. */
+int bpmd_unframe_batch(int role, int pmd_on, uint64_t msg_max, const uint8_t* d_wire, const uint64_t* d_wire_off,
+                       const uint32_t* d_wire_len, uint32_t n, bpmd_rd_state* d_state, uint8_t* d_out,
+                       const uint64_t* d_out_off, const uint32_t* d_out_cap, uint32_t* d_out_len, uint8_t* d_op,
+                       uint8_t* d_compressed, uint8_t* d_event, int32_t* d_status, uint32_t* d_consumed,
+                       uint8_t* d_ctl, uint8_t* d_ctl_len, uint16_t* d_close_code, void* stream);
+
+/* ---------------------------------------------------------------------
  * Context takeover: when no_context_takeover is not
  * negotiated, Beast's inflater keeps its window from message to message
  * (do_context_takeover_read -> inflate_stream::clear() is a no-op,
