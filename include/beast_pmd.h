@@ -144,7 +144,12 @@ int bpmd_inflate_reserve(void* stream, uint64_t in_bytes, uint64_t out_bytes, ui
  *   d_in + d_in_off[i], d_in_len[i]     message i
  *   d_out + d_out_off[i], d_out_cap[i]  output slot i (bpmd_deflate_upper_bound(len) always suffices)
  *   d_out_len[i]  payload bytes;  d_status[i]  0, or need_buffers if the
- *                 slot was too small (d_out_len[i] = 0, slot contents undefined) */
+ *                 slot was too small (d_out_len[i] = 0, slot contents undefined)
+ * A slot one byte larger than the payload is always accepted.  A slot of
+ * exactly the payload's size is accepted for a message of at most 4 KiB;
+ * for a longer one (and for every message of a context-takeover batch) it is
+ * refused when the last block is Huffman-coded and ends 1-5 bits into a byte.
+ * No byte outside [d_out_off[i], d_out_off[i] + d_out_cap[i]) is written. */
 int bpmd_deflate_batch(const bpmd_cfg* cfg, const uint8_t* d_in, const uint64_t* d_in_off,
                        const uint32_t* d_in_len, uint32_t n_msgs, uint8_t* d_out,
                        const uint64_t* d_out_off, const uint32_t* d_out_cap,
@@ -385,7 +390,10 @@ int bpmd_unframe_batch(int role, int pmd_on, uint64_t msg_max, const uint8_t* d_
  * after that connection's earlier output, whose last d_hist_len[i] bytes
  * (clamped to 2^windowBits) are the window.  One message per connection per
  * batch; connections run in parallel.  Statuses as bpmd_inflate_batch
- * (invalid_distance for a distance past the window).
+ * (invalid_distance for a distance past the window).  No byte outside
+ * [d_out_off[i], d_out_off[i] + d_out_cap[i]) is written, so a slot
+ * may end where the next connection's buffer begins.  A message that fails
+ * leaves its slot's contents past d_out_len[i] undefined.
  * ------------------------------------------------------------------- */
 int bpmd_inflate_takeover_batch(const bpmd_cfg* cfg, const uint8_t* d_in, const uint64_t* d_in_off,
                                 const uint32_t* d_in_len, const uint32_t* d_hist_len, uint32_t n_msgs,

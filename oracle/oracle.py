@@ -381,17 +381,21 @@ def pmd_deflate_stream(msgs, level=6, wbits=15, mem_level=4, strategy=0):
         L.bzo_deflate_free(z)
 
 
-def pmd_inflate_stream(payloads, cap: int = 1 << 20, wbits=15):
+def pmd_inflate_stream(payloads, cap=1 << 20, wbits=15):
     """One connection's messages through one inflater that keeps its window
-    (inflate_stream::clear() is a no-op, inflate_stream.ipp:49-53).  Returns
-    [(status, output)]."""
+    (inflate_stream::clear() is a no-op, inflate_stream.ipp:49-53).  `cap`:
+    one output capacity for every message, or a list of one per message.
+    Returns [(status, output)]."""
     L = lib()
     z = L.bzo_inflate_new()
     try:
         if L.bzo_inflate_reset(z, wbits):
             raise ValueError("windowBits out of range")
+        caps = [cap] * len(payloads) if isinstance(cap, int) else list(cap)
+        if len(caps) != len(payloads):
+            raise ValueError("one cap per payload")
         res = []
-        for p in payloads:
+        for p, cap in zip(payloads, caps):
             p = bytes(p)
             out = ctypes.create_string_buffer(max(cap, 1))
             got = ctypes.c_size_t(0)

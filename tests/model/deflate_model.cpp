@@ -133,15 +133,27 @@ static void put_tokens(BitW& bw, const std::vector<Tok>& toks, const uint8_t* w,
     bw.put(c.lcode[EOB], c.llen[EOB]);
 }
 
-// Encode one message; returns the pmd payload (tail stripped).
-static std::vector<uint8_t> encode(const uint8_t* msg, unsigned n, const Params& P)
+// Encode one message; returns the pmd payload (tail stripped).  hist_len < 0:
+// a message of a plain batch.  hist_len >= 0: a message of a context-takeover
+// batch with hist_len bytes of the connection's earlier plaintext before msg
+// in memory (pmd_deflate.hip deflate_impl with hist_len set): every message
+// takes the chunk path, so the chain limit is the multi-chunk one whatever
+// the length, and chunk 0's window starts min(hist_len, P.hist) bytes before
+// the message -- with any at all, chunk 0 takes the history segment floor.
+// The stored rules (chunk_stored's gain, INCOMP_STORED) still ask whether
+// the message itself is longer than one chunk.  hist0_min_seg: the segment
+// floor of chunk 0 with history (the kernel's BPMD_MIN_SEG_HIST, 32).
+static std::vector<uint8_t> encode(const uint8_t* msg, unsigned n, const Params& P, int64_t hist_len = -1,
+                                   unsigned hist0_min_seg = 32, uint32_t* bits = nullptr)
 {
+    const bool takeover = hist_len >= 0;
+    const unsigned hist0 = !takeover ? 0u : hist_len < (int64_t)P.hist ? (unsigned)hist_len : (unsigned)P.hist;
     std::vector<uint8_t> out;
     BitW bw;
     bw.out = &out;
     Level L = level_params(P.level);
     Params Q = P;   // the kernel's chain limit for this message
-    if (!Q.chain_cap) Q.chain_cap = (int)gpu_chain(P.level, n <= (unsigned)P.chunk);
+    if (!Q.chain_cap) Q.chain_cap = (int)gpu_chain(P.level, !takeover && n <= (unsigned)P.chunk);
     unsigned wsize = 1u << (P.wbits < 9 ? 9 : P.wbits);
     unsigned max_dist = wsize - LOOKAHEAD_MIN;
     std::vector<int32_t> prev;
@@ -158,9 +170,10 @@ static std::vector<uint8_t> encode(const uint8_t* msg, unsigned n, const Params&
     };
     for (unsigned base = 0; base < n; base += P.chunk) {
         unsigned cend = base + P.chunk < n ? base + P.chunk : n;
-        unsigned wb = base > (unsigned)P.hist ? base - P.hist : 0;
-        const uint8_t* w = msg + wb;
-        unsigned wn = cend - wb, a0 = base - wb;
+        // (deflate_chunk: back = min(base + hist, HIST))
+        unsigned back = base + hist0 < (unsigned)P.hist ? base + hist0 : (unsigned)P.hist;
+        const uint8_t* w = msg + base - back;   // before msg for chunk 0 of a message with history
+        unsigned wn = cend - base + back, a0 = back;
         std::vector<Tok> toks;
         bool chunk_incomp = false;
         if (L.parser != P_STORED) {
@@ -183,7 +196,8 @@ static std::vector<uint8_t> encode(const uint8_t* msg, unsigned n, const Params&
             chunk_incomp = no_parse;
             unsigned len = wn - a0;
             unsigned seg = (len + P.lanes - 1) / P.lanes;
-            const unsigned min_seg = a0 ? 32u : (unsigned)P.min_seg;   // (pmd_deflate.hip: history keeps 32)
+            // (pmd_deflate.hip: history keeps 32)
+            const unsigned min_seg = a0 ? (base ? 32u : hist0_min_seg) : (unsigned)P.min_seg;
             if (seg < min_seg) seg = min_seg;
             unsigned E = a0;
             for (unsigned s = a0; s < wn; s += seg) {
@@ -288,6 +302,7 @@ static std::vector<uint8_t> encode(const uint8_t* msg, unsigned n, const Params&
             put_tokens(bw, toks, w, dyn);
         }
     }
+    if (bits) *bits = (uint32_t)(out.size() * 8 + bw.n);   // payload bits before the tail
     // pmd tail: Flush::sync's empty stored block minus 00 00 FF FF
     bw.put(0, 3);
     bw.align();
@@ -303,6 +318,32 @@ extern "C" int64_t dmodel_batch(const uint8_t* data, const uint64_t* off, const 
     uint64_t pos = 0;
     for (uint32_t i = 0; i < n; ++i) {
         std::vector<uint8_t> e = encode(data + off[i], len[i], P);
+        if (pos + e.size() > out_cap) return -1;
+        memcpy(out + pos, e.data(), e.size());
+        out_off[i] = pos;
+        out_len[i] = (uint32_t)e.size();
+        pos += e.size();
+    }
+    return (int64_t)pos;
+}
+
+// A context-takeover batch: hist_len[i] bytes before data + off[i] are message
+// i's history (hist_len null: a plain batch).  out_bits, if given, takes each
+// payload's length in bits before the tail.  hist0_min_seg is a knob for
+// tests that show their inputs tell a wrong segment floor apart (the kernel's
+// value is 32).
+extern "C" int64_t dmodel_batch_hist(const uint8_t* data, const uint64_t* off, const uint32_t* len,
+                                     const uint32_t* hist_len, uint32_t n, int level, int wbits, int strategy, int chunk,
+                                     int hist, int hbits, int lanes, int min_seg, int chain_cap, int hist0_min_seg,
+                                     uint8_t* out, uint64_t out_cap, uint64_t* out_off, uint32_t* out_len,
+                                     uint32_t* out_bits)
+{
+    Params P{level, wbits, strategy, chunk, hist, hbits, lanes, min_seg, chain_cap};
+    uint64_t pos = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (hist_len && hist_len[i] > off[i]) return -2;
+        std::vector<uint8_t> e = encode(data + off[i], len[i], P, hist_len ? (int64_t)hist_len[i] : -1,
+                                         (unsigned)hist0_min_seg, out_bits ? out_bits + i : nullptr);
         if (pos + e.size() > out_cap) return -1;
         memcpy(out + pos, e.data(), e.size());
         out_off[i] = pos;

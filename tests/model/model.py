@@ -40,11 +40,26 @@ def lib():
         vp = ctypes.c_void_p
         _L.dmodel_batch.restype = ctypes.c_int64
         _L.dmodel_batch.argtypes = [vp, vp, vp, ctypes.c_uint32] + [ctypes.c_int] * 9 + [vp, ctypes.c_uint64, vp, vp]
+        _L.dmodel_batch_hist.restype = ctypes.c_int64
+        _L.dmodel_batch_hist.argtypes = [vp, vp, vp, vp, ctypes.c_uint32] + [ctypes.c_int] * 10 + \
+            [vp, ctypes.c_uint64, vp, vp, vp]
     return _L
 
 
-def encode(data, off, lens, level=6, wbits=15, strategy=0):
-    """Model payloads for the messages (data[off[i]:off[i]+lens[i]])."""
+MIN_SEG_HIST = 32   # BPMD_MIN_SEG_HIST (pmd_deflate.hip): segment floor of a chunk with history
+
+
+def encode(data, off, lens, level=6, wbits=15, strategy=0, hist=None, chain_cap=0, min_seg_hist=MIN_SEG_HIST,
+           bits=None):
+    """Model payloads for the messages (data[off[i]:off[i]+lens[i]]).
+
+    hist None: a plain batch.  hist = per-message byte counts: a context-
+    takeover batch (bpmd_deflate_takeover_batch), hist[i] bytes before
+    data[off[i]] being message i's history; the model clamps it to the level's
+    chunk history as the kernel does.  chain_cap (0 = the kernel's) and
+    min_seg_hist (chunk 0 with history) are there for tests that show a
+    wrong value would change the bytes.  bits: a list that receives each
+    payload's length in bits before the tail (where the last block ends)."""
     data = np.ascontiguousarray(data, dtype=np.uint8)
     off = np.ascontiguousarray(off, dtype=np.uint64)
     lens = np.ascontiguousarray(lens, dtype=np.uint32)
@@ -56,8 +71,29 @@ def encode(data, off, lens, level=6, wbits=15, strategy=0):
     out = np.zeros(cap, np.uint8)
     oo = np.zeros(n, np.uint64)
     ol = np.zeros(n, np.uint32)
-    hist = lib().dmodel_chunk_hist(level)   # lz::chunk_hist (lz_core.h): 2 KiB, 4 KiB at levels >= 7
-    r = lib().dmodel_batch(data.ctypes.data, off.ctypes.data, lens.ctypes.data, n, level, wbits, strategy, CHUNK,
-                           hist, HBITS, LANES, MIN_SEG, 0, out.ctypes.data, cap, oo.ctypes.data, ol.ctypes.data)
+    chunk_hist = lib().dmodel_chunk_hist(level)   # lz::chunk_hist (lz_core.h): 2 KiB, 4 KiB at levels >= 7
+    ob = np.zeros(n, np.uint32)
+    if hist is None and bits is None:
+        r = lib().dmodel_batch(data.ctypes.data, off.ctypes.data, lens.ctypes.data, n, level, wbits, strategy, CHUNK,
+                               chunk_hist, HBITS, LANES, MIN_SEG, chain_cap, out.ctypes.data, cap, oo.ctypes.data,
+                               ol.ctypes.data)
+    else:
+        hl = None if hist is None else np.ascontiguousarray(hist, dtype=np.uint32)
+        assert hl is None or (len(hl) == n and all(int(h) <= int(o) for h, o in zip(hl, off)))
+        r = lib().dmodel_batch_hist(data.ctypes.data, off.ctypes.data, lens.ctypes.data,
+                                    None if hl is None else hl.ctypes.data, n, level, wbits, strategy, CHUNK,
+                                    chunk_hist, HBITS, LANES, MIN_SEG, chain_cap, min_seg_hist, out.ctypes.data, cap,
+                                    oo.ctypes.data, ol.ctypes.data, ob.ctypes.data)
     assert r >= 0
+    if bits is not None:
+        bits[:] = ob.tolist()
     return [out[int(oo[i]):int(oo[i]) + int(ol[i])].tobytes() for i in range(n)]
+
+
+def encode_stream(plain, cuts, level=6, wbits=15, hist_cap=4096, **kw):
+    """One connection's takeover payloads: message k is plain[cuts[k]:cuts[k+1]]
+    with min(cuts[k], hist_cap) bytes of history (TakeoverDeflater.HIST)."""
+    plain = np.frombuffer(bytes(plain), dtype=np.uint8)
+    off = list(cuts[:-1])
+    lens = [b - a for a, b in zip(cuts, cuts[1:])]
+    return encode(plain, off, lens, level=level, wbits=wbits, hist=[min(o, hist_cap) for o in off], **kw)
