@@ -147,7 +147,8 @@ def test_c4_long_payloads_split_from_lanes():
     block-parallel (pmd_inflate_bp.hip) on a side stream from the
     longest-first order while the lane kernel takes the rest (pmd_capi.hip
     inflate_impl, bpmd_internal_lane_long_split; the wave kernel when
-    BPMD_INFLATE_BP=0).  Every message -- including corrupted long and short
+    BPMD_INFLATE_BP=0, a knob read once per process: that branch runs in a
+    child of tests/test_gpu_read_keyed.py).  Every message -- including corrupted long and short
     ones -- must equal the oracle's inflate in status and bytes."""
     import torch
     from beast_amd import pmd

@@ -68,9 +68,10 @@ def lanes_wave_split(split):
     return (L_UP_TO, split, False, False, G_NONE, NO3, W_OVER, split)
 
 
-@pytest.fixture(scope="module")
-def plan(tmp_path_factory):
-    d = tmp_path_factory.mktemp("inflate_plan")
+def load_plan(d):
+    """Compile the shim over inflate_plan.h into directory `d` (a pathlib
+    path) and return the plan function; tests/test_read_keyed_cases.py and
+    tests/test_gpu_read_keyed.py ask it which branch their batches take."""
     src, lib = d / "shim.cpp", d / "libplan.so"
     src.write_text(SHIM)
     subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-O1", "-shared", "-fPIC", "-I", CSRC, str(src), "-o",
@@ -85,6 +86,11 @@ def plan(tmp_path_factory):
 
     call.lib = L
     return call
+
+
+@pytest.fixture(scope="module")
+def plan(tmp_path_factory):
+    return load_plan(tmp_path_factory.mktemp("inflate_plan"))
 
 
 def test_knob_defaults(plan):
