@@ -113,7 +113,8 @@ const char* bpmd_version(void);
  *   d_in + d_in_off[i], d_in_len[i]   payload i without the 00 00 FF FF tail
  *   d_out + d_out_off[i], d_out_cap[i] output slot i
  *   d_out_len[i]  bytes produced;  d_status[i]  zlib::error of message i
- *                 (need_buffers = output exceeded d_out_cap[i]) */
+ *                 (need_buffers = output exceeded d_out_cap[i])
+ * No byte outside [d_out_off[i], d_out_off[i] + d_out_cap[i]) is written. */
 int bpmd_inflate_batch(const bpmd_cfg* cfg, const uint8_t* d_in, const uint64_t* d_in_off,
                        const uint32_t* d_in_len, uint32_t n_msgs, uint8_t* d_out,
                        const uint64_t* d_out_off, const uint32_t* d_out_cap,
