@@ -46,6 +46,7 @@ enum ScratchSlot : int {
     SCR_LONG_SPLIT = 9,      // long-payload split
     SCR_BP_STATS = 10,       // block-parallel inflate per-payload stats
     SCR_BP_DECODE = 11,      // block-parallel inflate decode workspace
+    SCR_SEND = 12,           // send side: wire sizes and their scan's workspace
 };
 // Small pinned host blocks per (device, stream): read-back targets
 enum PinnedSlot : int {

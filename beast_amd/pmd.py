@@ -823,3 +823,192 @@ def deflate_batch_multi(srcs, level: int = 6, window_bits: int = 15, mem_level: 
         res.append(Result(Batch(out, off, out_len), cap, status))
     totals = _multi(lib().bpmd_deflate_batch_multi, _Cfg(level, window_bits, mem_level, strategy, 0), parts)
     return res, totals
+
+
+# ------------------------------------------------------------------------
+# Send side: messages -> decision -> deflate -> frames -> packed wire
+# (bpmd_send_batch, bpmd_control_batch)
+
+CTL_WIRE = 144   # bytes of a control frame's wire slot
+
+
+def _send_lib():
+    """lib() with the send side's prototypes, bound on first use so that a
+    BPMD_LIB variant built without them still serves every other call"""
+    L = lib()
+    if not getattr(L, "_send_ready", False):
+        vp, u32, u64, ci = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int
+        L.bpmd_send_frame_bound.argtypes = [u64, u32, ci, ci]
+        L.bpmd_send_frame_bound.restype = u64
+        L.bpmd_send_wire_bound.argtypes = [u64, u32, ci, ci, ci]
+        L.bpmd_send_wire_bound.restype = u64
+        L.bpmd_send_batch.argtypes = ([ctypes.POINTER(_Cfg), vp, vp, vp, u32, ci, ci, u64, ci, u32] + [vp] * 9 + [u64]
+                                      + [vp] * 6)
+        L.bpmd_send_batch.restype = ci
+        L.bpmd_control_batch.argtypes = [vp, vp, vp, vp, vp, u32, vp, vp, vp, vp]
+        L.bpmd_control_batch.restype = ci
+        L.bpmd_internal_send_frames.argtypes = ([vp, vp, vp, u32, ci, ci, ci, u32] + [vp] * 7 + [u64] + [vp] * 6)
+        L.bpmd_internal_send_frames.restype = ci
+        L._send_ready = True
+    return L
+
+
+def send_frame_bound(n: int, frame_max: int = 4096, may_compress: bool = True, frag: bool = True) -> int:
+    """bpmd_send_frame_bound: the most frames (keys, in client role) a message
+    of n input bytes can take, whatever the decision and the deflater give."""
+    return _send_lib().bpmd_send_frame_bound(n, frame_max, int(may_compress), int(frag))
+
+
+def send_wire_bound(n: int, frame_max: int = 4096, masked: bool = False, may_compress: bool = True,
+                    frag: bool = True) -> int:
+    """bpmd_send_wire_bound: the most wire bytes of a message of n input bytes."""
+    return _send_lib().bpmd_send_wire_bound(n, frame_max, int(masked), int(may_compress), int(frag))
+
+
+def send_bounds(lens: torch.Tensor, frame_max: int = 4096, masked: bool = False, may_compress=True, frag: bool = True):
+    """(frame bound, wire bound) per message as int64 tensors on the lengths'
+    device: bpmd_send_frame_bound / bpmd_send_wire_bound without a host loop.
+    may_compress: one value, or a tensor with one per message."""
+    lens = lens.to(torch.int64)
+    mk = 4 if masked else 0
+    hdr = lambda x: torch.where(x <= 125, 2, torch.where(x <= 65535, 4, 10)) + mk  # noqa: E731
+
+    def plan(ln, multi):
+        if multi:
+            frames = torch.clamp((ln + frame_max - 1) // frame_max, min=1)
+            unit = torch.where(ln > 0, torch.full_like(ln, frame_max), ln)
+        else:
+            frames, unit = torch.ones_like(ln), ln
+        last = ln - (frames - 1) * unit
+        return frames, (frames - 1) * (hdr(unit) + unit) + hdr(last) + last
+
+    pf, pw = plan(lens, frag)
+    zf, zw = plan(lens + (lens + 7) // 8 + (lens + 63) // 64 + 11, True)
+    if isinstance(may_compress, torch.Tensor):
+        mc = may_compress.to(device=lens.device) != 0
+    else:
+        mc = torch.full_like(lens, bool(may_compress), dtype=torch.bool)
+    return torch.where(mc, torch.maximum(pf, zf), pf), torch.where(mc, torch.maximum(pw, zw), pw)
+
+
+@dataclass
+class Sent:
+    wire: Batch                # packed wire: off = exclusive sum of the sizes, len = size (0 = not written)
+    status: torch.Tensor       # int32: 0, WS_BAD_OPCODE, need_buffers or WS_BUFFER_OVERFLOW
+    compressed: torch.Tensor   # uint8: begin_msg's decision
+    total: torch.Tensor        # int64 [1]: the sum of all sizes, written or not
+    deflated: Result | None    # the staging slots (deflate_batch's result over the compressed messages)
+    key_base: torch.Tensor | None   # int32: message i's first key index (client role)
+
+
+def send_batch(src: Batch, role: int, pmd_on: bool = True, threshold: int = 0, frag: bool = True,
+               frame_max: int = 4096, op=None, opt=None, keys=None, key_base: torch.Tensor | None = None,
+               level: int = 6, window_bits: int = 15, mem_level: int = 4, strategy: int = 0, exact: bool = False,
+               staging: Result | None = None, wire: torch.Tensor | None = None, wire_cap: int | None = None,
+               stream=None) -> Sent:
+    """bpmd_send_batch: decide (begin_msg), deflate and frame every message of
+    `src` into one packed wire buffer, as write_some sends a message
+    (write.hpp:625-831); `role` is the sending end's (ROLE_CLIENT masks).
+    `op`: 1 text / 2 binary, per message or one value (None = binary); `opt`:
+    wr_compress_opt per message (None = on).  In client role frame f of
+    message i takes keys[key_base[i] + f]; without `key_base` the bases are
+    the exclusive sum of send_bounds' frame bounds and `keys` must hold at
+    least their sum.
+
+    Everything is enqueued on `stream`.  The call itself waits only to size
+    what it allocates: pass `staging` (a Result with the slots, e.g. an earlier
+    call's `deflated`), `key_base` and `wire` to avoid every wait.  `wire_cap`
+    defaults to the bytes of `wire`."""
+    L = _send_lib()
+    dev = src.data.device
+    n = src.n
+    masked = role == ROLE_CLIENT
+    with _on(stream):
+        opt_t = _u8(opt, n, dev)
+        op_t = _u8(op, n, dev)
+        may = (opt_t != 0) if (pmd_on and opt_t is not None) else bool(pmd_on)
+        fb = wb = None
+        if (masked and key_base is None) or wire is None:
+            fb, wb = send_bounds(src.len, frame_max, masked, may, frag)
+        kt = None
+        if masked:
+            if keys is None:
+                raise BpmdError("send_batch: client role needs keys")
+            nk = int(keys.numel()) if isinstance(keys, torch.Tensor) else len(keys)
+            kt = _keys(keys, nk, dev)
+            if key_base is None:
+                if kt.numel() < (int(fb.sum().item()) if n else 0):
+                    raise BpmdError("send_batch: keys must hold one key per frame of the bound (send_bounds)")
+                key_base = (torch.cumsum(fb, 0) - fb).to(torch.int32)
+        if pmd_on and staging is None:
+            ln = src.len.to(torch.int64)
+            cap = (ln + (ln + 7) // 8 + (ln + 63) // 64 + 11).to(torch.int32)
+            z_off = slot_offsets(cap)
+            z = torch.empty((int(z_off[-1].item() + cap[-1].item()) if n else 0) + 16, dtype=torch.uint8, device=dev)
+            staging = Result(Batch(z, z_off, torch.zeros(n, dtype=torch.int32, device=dev)), cap,
+                             torch.zeros(n, dtype=torch.int32, device=dev))
+        if wire is None:
+            wire = torch.empty((int(wb.sum().item()) if n else 0) + 16, dtype=torch.uint8, device=dev)
+            if wire_cap is None:
+                wire_cap = wire.numel() - 16
+        if wire_cap is None:
+            wire_cap = wire.numel()
+        if wire_cap > wire.numel():
+            raise BpmdError("send_batch: wire_cap exceeds the wire buffer")
+        w_off = torch.zeros(n, dtype=torch.int64, device=dev)
+        w_len = torch.zeros(n, dtype=torch.int32, device=dev)
+        comp = torch.zeros(n, dtype=torch.uint8, device=dev)
+        status = torch.zeros(n, dtype=torch.int32, device=dev)
+        total = torch.zeros(1, dtype=torch.int64, device=dev)
+    cfg = _Cfg(level, window_bits, mem_level, strategy, F_EXACT if exact else 0)
+    zs = staging
+    _check(L.bpmd_send_batch(ctypes.byref(cfg), _ptr(src.data), _ptr(src.off), _ptr(src.len), n, role,
+                             1 if pmd_on else 0, threshold, 1 if frag else 0, frame_max, _optr(op_t), _optr(opt_t),
+                             _optr(zs.out.data if zs else None), _optr(zs.out.off if zs else None),
+                             _optr(zs.cap if zs else None), _optr(zs.out.len if zs else None), _optr(kt),
+                             _optr(key_base), _ptr(wire), wire_cap, _ptr(w_off), _ptr(w_len), _ptr(comp),
+                             _ptr(status), _ptr(total), _stream_handle(stream)), "bpmd_send_batch")
+    return Sent(Batch(wire, w_off, w_len), status, comp, total, staging if pmd_on else None, key_base)
+
+
+@dataclass
+class Controls:
+    wire: Batch            # one frame per entry at 144 * i; len 0 = refused
+    status: torch.Tensor   # int32: 0, WS_BAD_CONTROL_SIZE or WS_BAD_OPCODE
+
+
+def control_batch(op, ctl: torch.Tensor, ctl_len, close_code=None, key=None, wire: torch.Tensor | None = None,
+                  stream=None) -> Controls:
+    """bpmd_control_batch: ping (9), pong (10) and close (8) frames as
+    write_ping / write_close build them (stream_impl.hpp:915-996).  `ctl`
+    (uint8 [n, 128]) and `ctl_len` are unframe_batch's control slots, so a
+    received ping's slot goes back out as a pong unchanged; a close with a
+    non-zero `close_code` carries the code and then the slot as its reason.
+    `key` (client role): one masking key per entry; `wire`: the caller's
+    buffer of 144 bytes per entry."""
+    L = _send_lib()
+    dev = ctl.device
+    n = int(ctl.numel()) // CTL_SLOT
+    if ctl.dtype != torch.uint8 or ctl.numel() != n * CTL_SLOT or not ctl.is_contiguous():
+        raise BpmdError("control_batch: ctl must be uint8 [n, 128]")
+    with _on(stream):
+        op_t = _u8(op, n, dev)
+        len_t = _u8(ctl_len, n, dev)
+        if close_code is None:
+            code = torch.zeros(n, dtype=torch.int16, device=dev)
+        elif isinstance(close_code, torch.Tensor):
+            code = close_code.to(device=dev, dtype=torch.int16).contiguous()
+        else:
+            a = np.array(np.broadcast_to(np.asarray(close_code, dtype=np.int64) & 0xFFFF, (n,)), dtype=np.uint16)
+            code = torch.from_numpy(a.view(np.int16)).to(dev)
+        k = _keys(key, n, dev)
+        if wire is None:
+            wire = torch.empty(n * CTL_WIRE + 16, dtype=torch.uint8, device=dev)
+        elif wire.dtype != torch.uint8 or wire.numel() < n * CTL_WIRE or not wire.is_contiguous():
+            raise BpmdError("control_batch: wire must hold 144 bytes per entry")
+        w_len = torch.zeros(n, dtype=torch.int32, device=dev)
+        status = torch.zeros(n, dtype=torch.int32, device=dev)
+        w_off = torch.arange(n, dtype=torch.int64, device=dev) * CTL_WIRE
+    _check(L.bpmd_control_batch(_ptr(op_t), _ptr(ctl), _ptr(len_t), _ptr(code), _optr(k), n, _ptr(wire), _ptr(w_len),
+                                _ptr(status), _stream_handle(stream)), "bpmd_control_batch")
+    return Controls(Batch(wire, w_off, w_len), status)

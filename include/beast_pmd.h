@@ -382,6 +382,95 @@ int bpmd_unframe_batch(int role, int pmd_on, uint64_t msg_max, const uint8_t* d_
                        uint8_t* d_ctl, uint8_t* d_ctl_len, uint16_t* d_close_code, void* stream);
 
 /* ---------------------------------------------------------------------
+ * Send side: from messages to packed wire bytes.  What write_some does per
+ * connection (websocket/impl/write.hpp:625-831) after begin_msg
+ * (websocket/impl/stream_impl.hpp:225-252), over a batch of messages, and the
+ * control frames of write_ping / write_close (stream_impl.hpp:915-996).
+ * ------------------------------------------------------------------- */
+
+/* Decide, deflate and frame a batch of messages in one chained call
+ * (bpmd_unframe_batch + bpmd_read_batch's counterpart).  `role` is the
+ * bpmd_role of the *sending* end: a client masks its frames.
+ *
+ * Message i (d_in + d_in_off[i], d_in_len[i] bytes, opcode d_op[i]: 1 text,
+ * 2 binary; NULL = all binary) is compressed iff pmd_on && d_opt[i] &&
+ * d_in_len[i] >= threshold (begin_msg; d_opt is wr_compress_opt per message,
+ * NULL = on; threshold is msg_size_threshold); d_compressed[i] tells.
+ *   - A compressed message is deflated as bpmd_deflate_batch does under cfg
+ *     (cfg->flags honoured) into its staging slot d_z + d_z_off[i] (d_z_cap[i]
+ *     bytes, d_z_len[i] produced: exactly bpmd_deflate_batch's out arrays,
+ *     caller-owned; bpmd_deflate_upper_bound sizes a slot) and goes out with
+ *     RSV1 in frames of at most frame_max payload bytes whatever `frag` says,
+ *     as Beast's deflate branch emits one frame per wr_buf fill
+ *     (write.hpp:655-703).  Messages that are not compressed reach the
+ *     deflater with length 0: each costs one byte of its staging slot, which
+ *     is ignored (a slot of 0 bytes is fine).
+ *   - An uncompressed message is framed straight from d_in: in frames of at
+ *     most frame_max bytes when frag != 0 (auto_fragment, :721-748, :795-829),
+ *     as one frame when frag == 0 (:706-720, :750-794).
+ *   An empty payload is one empty frame.  In client role frame f of message i
+ *   carries the key d_keys[d_key_base[i] + f] and is masked with it from the
+ *   key's first byte.  pmd_on == 0 runs no deflater: cfg and the staging
+ *   arrays may be NULL.
+ *
+ * The wire is packed: message i's frames start at d_wire + d_wire_off[i],
+ * the exclusive sum of the sizes before it, back to back in batch order with
+ * no padding; d_wire_len[i] is its size and *d_total the sum of all sizes.
+ * A message is written iff d_wire_off[i] + size <= wire_cap (bytes of
+ * d_wire); one that is not gets BPMD_WS_BUFFER_OVERFLOW and d_wire_len[i] = 0
+ * while *d_total still counts it, so the caller can grow the buffer and call
+ * again.  d_status[i], by precedence: BPMD_WS_BAD_OPCODE (d_op[i] not 1 or 2),
+ * the deflater's BPMD_NEED_BUFFERS, BPMD_WS_BUFFER_OVERFLOW (also for a
+ * message whose wire size exceeds 2^32 - 1), 0.  A message with one of the
+ * first two has size 0: it takes no room and its neighbours are packed as if
+ * it were absent.  No byte of d_wire at or beyond min(*d_total, wire_cap) is
+ * written, and none of a refused message's range.
+ *
+ * bpmd_send_frame_bound / bpmd_send_wire_bound (host only) give the most
+ * frames and the most wire bytes of a message of `len` input bytes over any
+ * decision (may_compress: pmd_on and the message's opt) and any deflate result
+ * within bpmd_deflate_upper_bound(len), so keys and wire are sized from input
+ * lengths alone; 0 for frame_max == 0.
+ *
+ * Everything is enqueued on `stream` and no step added here reads anything
+ * back; the one wait bpmd_deflate_batch has for messages over 4 KiB (its
+ * chunk count, above) is inherited when such a message is compressed.
+ * Until the call returns, d_wire_len holds the deflater's input lengths.
+ * Deliberately out of scope: context-takeover sends
+ * (bpmd_deflate_takeover_batch keeps its own layout) and a message that
+ * arrives in several write_some pieces.
+ * n == 0 is a no-op; BPMD_R_INVALID_ARGUMENT for frame_max == 0, a role that
+ * is neither value, client role without d_keys / d_key_base, a NULL required
+ * pointer, or (pmd_on) a cfg bpmd_deflate_batch refuses; BPMD_R_NO_DEVICE
+ * without a GPU. */
+uint64_t bpmd_send_frame_bound(uint64_t len, uint32_t frame_max, int may_compress, int frag);
+uint64_t bpmd_send_wire_bound(uint64_t len, uint32_t frame_max, int masked, int may_compress, int frag);
+int bpmd_send_batch(const bpmd_cfg* cfg, const uint8_t* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len,
+                    uint32_t n, int role, int pmd_on, uint64_t threshold, int frag, uint32_t frame_max,
+                    const uint8_t* d_op, const uint8_t* d_opt, uint8_t* d_z, const uint64_t* d_z_off,
+                    const uint32_t* d_z_cap, uint32_t* d_z_len, const uint32_t* d_keys, const uint32_t* d_key_base,
+                    uint8_t* d_wire, uint64_t wire_cap, uint64_t* d_wire_off, uint32_t* d_wire_len,
+                    uint8_t* d_compressed, int32_t* d_status, uint64_t* d_total, void* stream);
+
+/* Control frames (write_ping, write_close: stream_impl.hpp:915-996) over n
+ * entries: d_op[i] is 8 close, 9 ping or 10 pong; the payload is the
+ * d_ctl_len[i] bytes at d_ctl + 128 * i, the layout bpmd_unframe_batch
+ * writes, so a received ping's slot goes back out as a pong unchanged.  Ping
+ * and pong carry at most 125 bytes.  A close with d_close_code[i] != 0
+ * carries the code big-endian and then the slot's bytes as the reason, at
+ * most 123; a close with code 0 is empty whatever the slot holds.  Frames
+ * have FIN set and no RSV bits; with d_key (client role; NULL = server)
+ * entry i is masked with d_key[i] from the key's first byte.  One frame at
+ * d_wire + 144 * i, d_wire_len[i] bytes.  d_status[i]: 0,
+ * BPMD_WS_BAD_CONTROL_SIZE for an oversize entry, BPMD_WS_BAD_OPCODE for
+ * another opcode; both give length 0 and write nothing.  Asynchronous on
+ * `stream`; n == 0 is a no-op, BPMD_R_INVALID_ARGUMENT for a NULL pointer
+ * other than d_key. */
+int bpmd_control_batch(const uint8_t* d_op, const uint8_t* d_ctl, const uint8_t* d_ctl_len,
+                       const uint16_t* d_close_code, const uint32_t* d_key, uint32_t n, uint8_t* d_wire,
+                       uint32_t* d_wire_len, int32_t* d_status, void* stream);
+
+/* ---------------------------------------------------------------------
  * Context takeover: when no_context_takeover is not
  * negotiated, Beast's inflater keeps its window from message to message
  * (do_context_takeover_read -> inflate_stream::clear() is a no-op,
