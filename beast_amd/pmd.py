@@ -554,6 +554,106 @@ def _receive(wire, out_cap, inflate_cap, role, pmd_on, msg_max, state, out, out_
     return Received(u, u.event, status, inflated, zi)
 
 
+def _recv_lib():
+    """lib() with bpmd_receive_batch's prototype, bound on first use so that a
+    BPMD_LIB variant built without it still serves every other call"""
+    L = lib()
+    if not getattr(L, "_recv_ready", False):
+        vp, u32, ci = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int
+        L.bpmd_receive_work_bytes.argtypes = [u32]
+        L.bpmd_receive_work_bytes.restype = ctypes.c_size_t
+        L.bpmd_receive_batch.argtypes = [ctypes.POINTER(_Cfg), ci, ci, ctypes.c_uint64, vp, vp, vp, u32] + [vp] * 19
+        L.bpmd_receive_batch.restype = ci
+        L._recv_ready = True
+    return L
+
+
+def _host_slots(what: str, n: int, dev, cap, buf, off):
+    """_out_slots without a wait: one capacity for all entries sizes the
+    buffer on the host; capacities in a tensor need the caller's buffer."""
+    if isinstance(cap, int):
+        stride = (cap + 15) // 16 * 16
+        if off is None:
+            off = torch.arange(n, dtype=torch.int64, device=dev) * stride
+        if buf is None:
+            buf = torch.empty(n * stride + 16, dtype=torch.uint8, device=dev)
+        return torch.full((n,), cap, dtype=torch.int32, device=dev), buf, off
+    if buf is None or off is None:
+        raise BpmdError(f"recv_batch: {what} capacities in a tensor need the {what} buffer and its offsets")
+    return cap.to(device=dev, dtype=torch.int32), buf, off
+
+
+@dataclass
+class Recv:
+    frames: Unframed       # the frame pass's results, entry by entry; frames.out holds the uncompressed messages
+    msg: Batch             # the inflated messages' slots; msg.len = every complete message's length (d_msg_len)
+    event: torch.Tensor    # uint8 EV_* (frames.event)
+    status: torch.Tensor   # int32: 0, a WS_* error, BAD_FRAME_PAYLOAD or a zlib::error (frames.status, merged in place)
+
+    def to_host(self):
+        """Per entry: the message's bytes after EV_MESSAGE with status 0 or
+        BAD_FRAME_PAYLOAD (from the slot frames.compressed names), else None."""
+        ev, st = self.event.cpu().tolist(), self.status.cpu().tolist()
+        comp, ln = self.frames.compressed.cpu().tolist(), self.msg.len.cpu().tolist()
+        msgs = []
+        for i, e in enumerate(ev):
+            if e != EV_MESSAGE or st[i] not in (0, BAD_FRAME_PAYLOAD):
+                msgs.append(None)
+                continue
+            b = self.msg if comp[i] else self.frames.out
+            o = int(b.off[i])
+            msgs.append(bytes(b.data[o:o + ln[i]].cpu().numpy().tobytes()))
+        return msgs
+
+
+def recv_batch(wire: Batch, out_cap, msg_cap, role: int, pmd_on: bool = True, msg_max: int = 16 << 20,
+               state: torch.Tensor | None = None, out: torch.Tensor | None = None,
+               out_off: torch.Tensor | None = None, msg: torch.Tensor | None = None,
+               msg_off: torch.Tensor | None = None, window_bits: int = 15, stream=None) -> Recv:
+    """bpmd_receive_batch: from wire bytes to checked messages in one chained
+    call (read.hpp:1063-1385): the frame pass of unframe_batch, the inflater
+    over the entries that completed a compressed message (gathered slot ->
+    message slot of `msg_cap` bytes), rd_msg_max on the inflated size
+    (WS_MESSAGE_TOO_BIG; WS_BUFFER_OVERFLOW when the slot is the smaller) and
+    the UTF-8 check of text where the message lies (BAD_FRAME_PAYLOAD).
+    Everything is enqueued on `stream` and the call never waits: `out_cap` /
+    `msg_cap` as one int size their buffers here, as tensors they need `out` +
+    `out_off` / `msg` + `msg_off`.  With pmd_on False nothing is inflated and
+    `msg` has no bytes."""
+    L = _recv_lib()
+    dev = wire.data.device
+    n = wire.n
+    if state is not None and (state.dtype != torch.uint8 or state.numel() != n * RD_STATE_BYTES
+                              or not state.is_contiguous()):
+        raise BpmdError("recv_batch: state must be rd_state(n)")
+    with _on(stream):
+        cap, out, out_off = _host_slots("out", n, dev, out_cap, out, out_off)
+        out_len = torch.empty(n, dtype=torch.int32, device=dev)
+        u8 = lambda *shape: torch.empty(shape, dtype=torch.uint8, device=dev)  # noqa: E731
+        op, comp, event, ctl_len, ctl = u8(n), u8(n), u8(n), u8(n), u8(n, CTL_SLOT)
+        status = torch.empty(n, dtype=torch.int32, device=dev)
+        consumed = torch.empty(n, dtype=torch.int32, device=dev)
+        code = torch.empty(n, dtype=torch.int16, device=dev)
+        msg_len = torch.empty(n, dtype=torch.int32, device=dev)
+        mcap = work = None
+        if pmd_on:
+            mcap, msg, msg_off = _host_slots("msg", n, dev, msg_cap, msg, msg_off)
+            work = u8(max(int(L.bpmd_receive_work_bytes(n)), 1))
+        else:
+            msg, msg_off = u8(0), torch.zeros(n, dtype=torch.int64, device=dev)
+    cfg = _Cfg(0, window_bits, 8, 0, 0)
+    _check(L.bpmd_receive_batch(ctypes.byref(cfg) if pmd_on else None, role, 1 if pmd_on else 0, msg_max, _ptr(wire.data), _ptr(wire.off),
+                                _ptr(wire.len), n, _optr(state), _ptr(out), _ptr(out_off), _ptr(cap), _ptr(out_len),
+                                _ptr(op), _ptr(comp), _ptr(event), _ptr(status), _ptr(consumed), _ptr(ctl),
+                                _ptr(ctl_len), _ptr(code), _ptr(msg) if pmd_on else None,
+                                _ptr(msg_off) if pmd_on else None, _optr(mcap), _ptr(msg_len), _optr(work),
+                                _stream_handle(stream)), "bpmd_receive_batch")
+    with _on(stream):
+        code = code.to(torch.int32) & 0xFFFF
+    frames = Unframed(Batch(out, out_off, out_len), cap, op, comp, event, status, consumed, ctl, ctl_len, code, state)
+    return Recv(frames, Batch(msg, msg_off, msg_len), event, status)
+
+
 # ------------------------------------------------------------------------
 # Context takeover (SURVEY.md §8(f) N3)
 

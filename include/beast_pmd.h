@@ -381,6 +381,67 @@ int bpmd_unframe_batch(int role, int pmd_on, uint64_t msg_max, const uint8_t* d_
                        uint8_t* d_compressed, uint8_t* d_event, int32_t* d_status, uint32_t* d_consumed,
                        uint8_t* d_ctl, uint8_t* d_ctl_len, uint16_t* d_close_code, void* stream);
 
+/* Unframe, inflate and check a batch of connections in one chained call
+ * (bpmd_send_batch's counterpart): what read_some delivers per connection
+ * (read.hpp:1063-1385), the inflater with rd_msg_max applied to the inflated
+ * size (:1357-1367) and the UTF-8 check of text (:1372-1384) included.
+ *
+ * The arguments from d_wire to d_close_code are exactly bpmd_unframe_batch's
+ * and every output of the frame pass keeps the meaning documented there,
+ * d_out_len included (the gathered, still compressed length); only d_status
+ * can change afterwards, and only for an entry with BPMD_EV_MESSAGE and frame
+ * status 0.  Such an entry holds a complete message:
+ *   - d_compressed[i] != 0: the gathered payload is inflated as
+ *     bpmd_inflate_batch does under cfg->window_bits (cfg->flags must not
+ *     carry BPMD_F_RAW) into the message slot d_msg + d_msg_off[i], of which
+ *     the inflater may use min(d_msg_cap[i], msg_max + 1) bytes (all of
+ *     d_msg_cap[i] when msg_max == 0): the effective capacity.
+ *     d_msg_len[i] is the number of bytes produced, at most that capacity.
+ *     d_status[i]: a zlib::error other than need_buffers as the inflater
+ *     reports it, in stream order, so an error that precedes the limit wins;
+ *     BPMD_WS_MESSAGE_TOO_BIG for a message that inflates to more than
+ *     msg_max bytes when msg_max <= d_msg_cap[i]; BPMD_WS_BUFFER_OVERFLOW for
+ *     one that outgrows d_msg_cap[i] when that is the smaller; else as below.
+ *   - d_compressed[i] == 0: the message stays in its gathered slot in d_out
+ *     and d_msg_len[i] = d_out_len[i].
+ *   A text message (d_op[i] == 1) with status 0 so far is checked where it
+ *   lies, as bpmd_utf8_check_batch does; any verdict but valid gives
+ *   BPMD_BAD_FRAME_PAYLOAD.
+ * Every other entry keeps the frame pass's event and status and gets
+ * d_msg_len[i] = 0.  After the call d_compressed[i] tells which slot holds
+ * message i.
+ *
+ * No byte of d_msg outside [d_msg_off[i], d_msg_off[i] + effective capacity)
+ * is written and none of an entry that was not inflated; d_wire is not
+ * modified, d_out only by the frame pass.  pmd_on == 0 runs no inflater: cfg,
+ * d_msg, d_msg_off, d_msg_cap, d_msg_len and d_work may be NULL.
+ *
+ * d_work: bpmd_receive_work_bytes(n) (host only) bytes of device memory the
+ * call may overwrite: per entry the inflater's input length, its effective
+ * capacity, the text flag of its output and its status.  The caller owns it
+ * because the inflater takes the stream's launch lock itself, so nothing of
+ * this call may live in the stream's scratch across it; one workspace serves
+ * one call at a time.
+ *
+ * Everything is enqueued on `stream` and no step added here reads anything
+ * back; the one wait bpmd_inflate_batch has on a stream's first
+ * block-parallel call (above) is inherited, and bpmd_inflate_reserve removes
+ * it.  Deliberately out of scope: context-takeover receives
+ * (bpmd_inflate_takeover_batch keeps its own layout), more than one event per
+ * entry and call, and partial frames (bpmd_unframe_batch, above).
+ * n == 0 is a no-op; BPMD_R_INVALID_ARGUMENT for a role that is neither
+ * value, a NULL required pointer, BPMD_F_RAW or (pmd_on) a NULL cfg;
+ * BPMD_R_DOMAIN_ERROR for window bits outside 8..15; BPMD_R_NO_DEVICE
+ * without a GPU. */
+size_t bpmd_receive_work_bytes(uint32_t n);
+int bpmd_receive_batch(const bpmd_cfg* cfg, int role, int pmd_on, uint64_t msg_max, const uint8_t* d_wire,
+                       const uint64_t* d_wire_off, const uint32_t* d_wire_len, uint32_t n, bpmd_rd_state* d_state,
+                       uint8_t* d_out, const uint64_t* d_out_off, const uint32_t* d_out_cap, uint32_t* d_out_len,
+                       uint8_t* d_op, uint8_t* d_compressed, uint8_t* d_event, int32_t* d_status,
+                       uint32_t* d_consumed, uint8_t* d_ctl, uint8_t* d_ctl_len, uint16_t* d_close_code,
+                       uint8_t* d_msg, const uint64_t* d_msg_off, const uint32_t* d_msg_cap, uint32_t* d_msg_len,
+                       void* d_work, void* stream);
+
 /* ---------------------------------------------------------------------
  * Send side: from messages to packed wire bytes.  What write_some does per
  * connection (websocket/impl/write.hpp:625-831) after begin_msg
