@@ -22,9 +22,10 @@
 // of a call lives in the stream's shared scratch while the stream's launch
 // lock is released around step 3 (bpmd_inflate_batch takes that lock itself).
 //
-// The finish kernel follows utf8_kernel's data path (pmd_frame.hip): one wave
-// per entry, 16 bytes per lane per step in aligned 16-byte loads plus 4
-// look-ahead bytes, the all-ASCII early out, span flags at the two ragged
+// The finish kernel follows utf8_kernel's data path (pmd_frame.hip; the walk
+// is utf8_fails in receive_common.h, shared with pmd_receive_takeover.hip):
+// one wave per entry, 16 bytes per lane per step in aligned 16-byte loads plus
+// 4 look-ahead bytes, the all-ASCII early out, span flags at the two ragged
 // edges.  Most entries of a batch need no byte pass at all (binary, refused,
 // incomplete): their wave reads the entry's plan and goes on.  No wave waits
 // for another.
@@ -33,14 +34,11 @@
 
 #include "../../include/beast_pmd.h"
 #include "pmd_internal.h"
+#include "receive_common.h"
 #include "receive_plan.h"
-#include "utf8_unit.h"
 
 namespace bpmd {
 namespace recv {
-
-constexpr unsigned WAVE = 64;
-constexpr unsigned WPB = 4;   // waves (entries in flight) per block
 
 // step 2: receive_plan.h's select per entry
 __global__ void __launch_bounds__(256)
@@ -55,44 +53,6 @@ recv_select_kernel(const uint8_t* __restrict__ event, const int32_t* __restrict_
     z_in_len[i] = s.in_len;
     z_cap[i] = s.eff_cap;
     z_text[i] = (uint8_t)s.text;
-}
-
-// utf8_kernel's walk over one message (pmd_frame.hip), the verdict reduced to
-// valid or not: true when the nb bytes at p are not well-formed UTF-8 or stop
-// inside a code point.  Wave-uniform result.
-__device__ __forceinline__ bool utf8_fails(const uint8_t* __restrict__ p, uint32_t nb, unsigned lane)
-{
-    using frame::H;
-    if (nb == 0) return false;
-    const uint32_t s = (uint32_t)((uintptr_t)p & 15u);
-    const uint8_t* base = p - s;
-    const uint32_t units = (s + nb + 15u) >> 4, end = s + nb;
-    bool err = false, inc = false;
-    for (uint32_t u0 = 0; u0 < units; u0 += WAVE) {
-        const uint32_t u = u0 + lane, b0 = u * 16;
-        uint4 w = make_uint4(0, 0, 0, 0);
-        if (u < units) w = *(const uint4*)(base + b0);
-        uint32_t nxt = __shfl_down(w.x, 1);
-        if (lane == WAVE - 1) nxt = (b0 + 16 < end) ? *(const uint32_t*)(base + b0 + 16) : 0u;
-        if (u >= units) continue;
-        if (((w.x | w.y | w.z | w.w | nxt) & H) == 0) continue;   // all ASCII: nothing to reject
-        const uint32_t x[5] = {w.x, w.y, w.z, w.w, nxt};
-        if (b0 >= s && b0 + 20 <= end) {   // unit and look-ahead inside the message
-            const uint32_t v[5] = {H, H, H, H, H};
-            frame::utf8_unit(x, v, err, inc);
-        } else {
-            uint32_t v[5];
-#pragma unroll
-            for (int d = 0; d < 5; ++d)
-                v[d] = frame::span_flags((int32_t)s - (int32_t)(b0 + 4 * d), (int32_t)end - (int32_t)(b0 + 4 * d));
-            frame::utf8_unit(x, v, err, inc);
-        }
-        if (u == 0) {   // the first byte must start a code point
-            const uint32_t f = x[s >> 2] >> (8 * (s & 3));
-            err = err || (f & 0xC0u) == 0x80u;
-        }
-    }
-    return __any(err || inc) != 0;
 }
 
 // step 4: one wave per entry.  zst == nullptr: permessage-deflate is off,
@@ -139,30 +99,11 @@ using namespace bpmd;
 
 namespace {
 unsigned elem_grid(uint32_t n) { return (n + 255u) / 256u; }
-unsigned wave_grid(uint32_t n)
-{
-    const unsigned want = (n + recv::WPB - 1) / recv::WPB, cap = (unsigned)cu_count() * 8u;
-    return want < cap ? want : cap;
-}
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-// the workspace: three 32-bit arrays and a byte array, each from a 256-byte boundary
-struct Work {
-    uint32_t *z_in_len, *z_cap;
-    int32_t* zst;
-    uint8_t* z_text;
-};
-Work carve(void* d_work, uint32_t n)
-{
-    uint8_t* p = (uint8_t*)d_work;
-    const size_t a = align256((size_t)n * sizeof(uint32_t));
-    return Work{(uint32_t*)p, (uint32_t*)(p + a), (int32_t*)(p + 2 * a), p + 3 * a};
-}
 }  // namespace
 
 extern "C" size_t bpmd_receive_work_bytes(uint32_t n)
 {
-    return 3 * align256((size_t)n * sizeof(uint32_t)) + align256((size_t)n);
+    return 3 * recv::align256((size_t)n * sizeof(uint32_t)) + recv::align256((size_t)n);
 }
 
 // Inherited from bpmd_inflate_batch: a stream's first block-parallel call
@@ -196,9 +137,9 @@ extern "C" int bpmd_receive_batch(const bpmd_cfg* cfg, int role, int pmd_on, uin
                        d_out_off, d_out_cap, d_out_len, d_op, d_compressed, d_event, d_status, d_consumed, d_ctl,
                        d_ctl_len, d_close_code, s))
         return BPMD_R_HIP_ERROR;
-    Work w{nullptr, nullptr, nullptr, nullptr};
+    recv::Work w{nullptr, nullptr, nullptr, nullptr};
     if (pmd_on) {
-        w = carve(d_work, n);
+        w = recv::carve(d_work, n);
         hipLaunchKernelGGL(recv::recv_select_kernel, dim3(elem_grid(n)), dim3(256), 0, s, d_event, d_status,
                            d_compressed, d_op, d_out_len, d_msg_cap, msg_max, n, w.z_in_len, w.z_cap, w.z_text);
         if (hipGetLastError() != hipSuccess) return BPMD_R_HIP_ERROR;
@@ -207,8 +148,8 @@ extern "C" int bpmd_receive_batch(const bpmd_cfg* cfg, int role, int pmd_on, uin
                                stream);
         if (r) return r;
     }
-    hipLaunchKernelGGL(recv::recv_finish_kernel, dim3(wave_grid(n)), dim3(recv::WAVE * recv::WPB), 0, s, d_event,
-                       d_compressed, d_op, d_out, d_out_off, d_out_len, d_msg, d_msg_off, d_msg_cap, msg_max, w.zst, n,
-                       d_msg_len, d_status);
+    hipLaunchKernelGGL(recv::recv_finish_kernel, dim3(recv::wave_grid(n)), dim3(recv::WAVE * recv::WPB), 0, s,
+                       d_event, d_compressed, d_op, d_out, d_out_off, d_out_len, d_msg, d_msg_off, d_msg_cap, msg_max,
+                       w.zst, n, d_msg_len, d_status);
     return hipGetLastError() != hipSuccess ? BPMD_R_HIP_ERROR : BPMD_R_OK;
 }

@@ -1,8 +1,9 @@
 // utf8_unit.h -- the unit step of the UTF-8 check (websocket/detail/
 // utf8_checker.ipp:39-315 restated over 16-byte units): what utf8_kernel
-// (pmd_frame.hip) and recv_finish_kernel (pmd_receive.hip) run per lane on 16
-// bytes and the 4 bytes after them.  The callers load the bytes and say which
-// of them lie inside the message.
+// (pmd_frame.hip) and utf8_fails (receive_common.h, for the finish kernels of
+// pmd_receive.hip and pmd_receive_takeover.hip) run per lane on 16 bytes and
+// the 4 bytes after them.  The callers load the bytes and say which of them
+// lie inside the message.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

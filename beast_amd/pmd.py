@@ -722,6 +722,98 @@ class TakeoverInflater:
         return Result(Batch(self.buf, out_off, out_len), cap, status)
 
 
+def _recv_tk_lib():
+    """lib() with bpmd_receive_takeover_batch's prototype, bound on first use
+    as _recv_lib binds bpmd_receive_batch's"""
+    L = lib()
+    if not getattr(L, "_recv_tk_ready", False):
+        vp, u32, ci = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int
+        L.bpmd_receive_takeover_work_bytes.argtypes = [u32]
+        L.bpmd_receive_takeover_work_bytes.restype = ctypes.c_size_t
+        L.bpmd_receive_takeover_batch.argtypes = [ctypes.POINTER(_Cfg), ci, ctypes.c_uint64, vp, vp, vp, u32] + \
+            [vp] * 15 + [u32] + [vp] * 6
+        L.bpmd_receive_takeover_batch.restype = ci
+        L._recv_tk_ready = True
+    return L
+
+
+class TakeoverReceiver:
+    """bpmd_receive_takeover_batch over n_conn context-takeover connections:
+    recv_batch's chained call (frame pass, inflater, rd_msg_max, UTF-8 check)
+    with TakeoverInflater's buffers -- 2 * 2^window_bits + max_msg bytes per
+    connection, the next message decoded right behind the earlier output, the
+    window slid to the front when a message would not fit -- and that
+    bookkeeping done on the device, so recv never waits.  Entry i of every
+    batch is connection i.  The receiver owns the connections' buffers (`buf`,
+    `base`, `pos`), their message states (`rd_state`), the gathered slots and
+    the workspace; a Recv's tensors of one call are valid until the next.  A
+    connection whose message fails in the inflater (a zlib::error,
+    WS_BUFFER_OVERFLOW, or WS_MESSAGE_TOO_BIG with the limit outgrown) keeps
+    its position and an undefined window: drop it, as with TakeoverInflater."""
+
+    def __init__(self, n_conn: int, role: int, window_bits: int = 15, max_msg: int = 1 << 16,
+                 msg_max: int = 16 << 20, device="cuda"):
+        L = _recv_tk_lib()
+        self.n, self.role, self.wbits, self.msg_max = n_conn, role, window_bits, msg_max
+        self.W = 1 << window_bits
+        self.max_msg = max_msg
+        self.slot = (2 * self.W + max_msg + 15) // 16 * 16
+        self.buf = torch.zeros(n_conn * self.slot + 16, dtype=torch.uint8, device=device)
+        self.base = torch.arange(n_conn, dtype=torch.int64, device=device) * self.slot
+        self.pos = torch.zeros(n_conn, dtype=torch.int32, device=device)
+        self.rd_state = rd_state(n_conn, device)
+        self.work = torch.empty(max(int(L.bpmd_receive_takeover_work_bytes(n_conn)), 1), dtype=torch.uint8,
+                                device=device)
+        self._out_cap = self._out = self._out_off = None
+
+    def recv(self, wire: Batch, out_cap: int, msg_cap=None, stream=None) -> Recv:
+        """One call over wire (entry i: connection i's bytes; an idle connection
+        sends length 0).  `out_cap`: bytes of every gathered slot, one int, the
+        same in every call (the slots keep a message's fragments from call to
+        call).  `msg_cap`: the most a message may inflate to, one int or an
+        int32 tensor, default and at most max_msg.  Recv.msg is Batch(buf,
+        msg_off, msg_len): an inflated message lies in its connection's buffer,
+        an uncompressed one in frames.out."""
+        L = _recv_tk_lib()
+        dev = self.buf.device
+        n = wire.n
+        if n != self.n:
+            raise BpmdError("TakeoverReceiver.recv: one entry per connection")
+        if not isinstance(out_cap, int) or (self._out_cap is not None and out_cap != self._out_cap):
+            raise BpmdError("TakeoverReceiver.recv: out_cap is one int, the same in every call")
+        if isinstance(msg_cap, int) and msg_cap > self.max_msg:
+            raise BpmdError("msg_cap exceeds max_msg")
+        with _on(stream):
+            if self._out_cap is None:
+                _, self._out, self._out_off = _host_slots("out", n, dev, out_cap, None, None)
+                self._out_cap = out_cap
+            cap = torch.full((n,), out_cap, dtype=torch.int32, device=dev)
+            if msg_cap is None or isinstance(msg_cap, int):
+                mcap = torch.full((n,), self.max_msg if msg_cap is None else msg_cap, dtype=torch.int32, device=dev)
+            else:   # the call itself clamps a capacity to the room of a connection's buffer
+                mcap = msg_cap.to(device=dev, dtype=torch.int32)
+            out_len = torch.empty(n, dtype=torch.int32, device=dev)
+            u8 = lambda *shape: torch.empty(shape, dtype=torch.uint8, device=dev)  # noqa: E731
+            op, comp, event, ctl_len, ctl = u8(n), u8(n), u8(n), u8(n), u8(n, CTL_SLOT)
+            status = torch.empty(n, dtype=torch.int32, device=dev)
+            consumed = torch.empty(n, dtype=torch.int32, device=dev)
+            code = torch.empty(n, dtype=torch.int16, device=dev)
+            msg_len = torch.empty(n, dtype=torch.int32, device=dev)
+            msg_off = torch.empty(n, dtype=torch.int64, device=dev)
+        cfg = _Cfg(0, self.wbits, 8, 0, 0)
+        _check(L.bpmd_receive_takeover_batch(
+            ctypes.byref(cfg), self.role, self.msg_max, _ptr(wire.data), _ptr(wire.off), _ptr(wire.len), n,
+            _ptr(self.rd_state), _ptr(self._out), _ptr(self._out_off), _ptr(cap), _ptr(out_len), _ptr(op), _ptr(comp),
+            _ptr(event), _ptr(status), _ptr(consumed), _ptr(ctl), _ptr(ctl_len), _ptr(code), _ptr(self.buf),
+            _ptr(self.base), self.slot, _ptr(self.pos), _ptr(mcap), _ptr(msg_off), _ptr(msg_len), _ptr(self.work),
+            _stream_handle(stream)), "bpmd_receive_takeover_batch")
+        with _on(stream):
+            code = code.to(torch.int32) & 0xFFFF
+        frames = Unframed(Batch(self._out, self._out_off, out_len), cap, op, comp, event, status, consumed, ctl,
+                          ctl_len, code, self.rd_state)
+        return Recv(frames, Batch(self.buf, msg_off, msg_len), event, status)
+
+
 # ------------------------------------------------------------------------
 # Cross-connection micro-batcher (SURVEY.md §8(f) N2)
 

@@ -427,8 +427,9 @@ int bpmd_unframe_batch(int role, int pmd_on, uint64_t msg_max, const uint8_t* d_
  * back; the one wait bpmd_inflate_batch has on a stream's first
  * block-parallel call (above) is inherited, and bpmd_inflate_reserve removes
  * it.  Deliberately out of scope: context-takeover receives
- * (bpmd_inflate_takeover_batch keeps its own layout), more than one event per
- * entry and call, and partial frames (bpmd_unframe_batch, above).
+ * (bpmd_receive_takeover_batch, below, is this call over connection buffers),
+ * more than one event per entry and call, and partial frames
+ * (bpmd_unframe_batch, above).
  * n == 0 is a no-op; BPMD_R_INVALID_ARGUMENT for a role that is neither
  * value, a NULL required pointer, BPMD_F_RAW or (pmd_on) a NULL cfg;
  * BPMD_R_DOMAIN_ERROR for window bits outside 8..15; BPMD_R_NO_DEVICE
@@ -635,6 +636,76 @@ void bpmd_pmd_normalize(bpmd_pmd_offer* offer);
  * only when d_pos[i] >= 2 * d_keep[i], so the ranges never overlap). */
 int bpmd_slide_batch(uint8_t* d_buf, const uint64_t* d_base, const uint32_t* d_pos, const uint32_t* d_keep,
                      uint32_t n, void* stream);
+
+/* Unframe, inflate with context takeover and check a batch of connections in
+ * one chained call: bpmd_receive_batch for connections whose inflater keeps
+ * its window (above), which is what Beast negotiates by default.  Entry i is
+ * connection i, as d_state[i] already is; a connection takes part in a call
+ * once.  pmd_on is implied.
+ *
+ * The arguments from d_wire to d_close_code are exactly bpmd_unframe_batch's
+ * and every output of the frame pass keeps the meaning documented there;
+ * afterwards only d_status can change, as in bpmd_receive_batch.
+ *
+ * Connection i owns the slot_bytes bytes at d_buf + d_base[i], of which the
+ * first d_pos[i] hold its latest output: the last min(d_pos[i], W) of them,
+ * W = 2^cfg->window_bits, are its window.  d_pos is in/out; a new connection
+ * starts at 0 and d_pos[i] never exceeds slot_bytes.  slot_bytes > 2 * W.
+ * "The message capacity" of entry i is min(d_msg_cap[i], slot_bytes - 2 * W)
+ * everywhere below, and the effective capacity is that limited to msg_max + 1
+ * bytes (all of it when msg_max == 0), as in bpmd_receive_batch.
+ *   - An entry that completed a compressed message (BPMD_EV_MESSAGE, frame
+ *     status 0, d_compressed[i] != 0) is inflated right behind the
+ *     connection's earlier output.  If d_pos[i] + effective capacity >
+ *     slot_bytes, the W bytes before d_pos[i] are first moved to the buffer's
+ *     front and d_pos[i] becomes W (then d_pos[i] was more than 2 * W, so the
+ *     move never overlaps itself).  d_msg_off[i] (an output) = d_base[i] +
+ *     that position: where message i lies in d_buf.  d_msg_len[i] is the
+ *     number of bytes produced, at most the effective capacity.  d_status[i]:
+ *     bpmd_receive_batch's rule with the message capacity above -- a
+ *     zlib::error as the inflater reports it, in stream order (invalid_distance
+ *     for a distance past the window), BPMD_WS_MESSAGE_TOO_BIG,
+ *     BPMD_WS_BUFFER_OVERFLOW, BPMD_BAD_FRAME_PAYLOAD for text that is not
+ *     UTF-8 (checked in the connection's buffer), or 0.
+ *     d_pos[i] advances by d_msg_len[i] iff the inflater's own status is 0:
+ *     also when the merged status is BPMD_WS_MESSAGE_TOO_BIG or
+ *     BPMD_BAD_FRAME_PAYLOAD, since Beast's window has taken those bytes too
+ *     (and the connection fails anyway).  After a zlib::error or an outgrown
+ *     capacity d_pos[i] stays, the window is undefined from then on and the
+ *     caller drops the connection, as with pmd.py's TakeoverInflater.
+ *   - Every other entry leaves its connection alone: no slide, d_pos[i]
+ *     unchanged, d_msg_off[i] = d_base[i] + d_pos[i].  A complete uncompressed
+ *     message stays in its gathered slot in d_out (d_msg_len[i] =
+ *     d_out_len[i], text checked there); any other entry gets d_msg_len[i] = 0.
+ *
+ * The only bytes of d_buf written are, per entry, [d_base[i], d_base[i] + W)
+ * of a connection that slid and [d_msg_off[i], d_msg_off[i] + effective
+ * capacity) of an inflated entry (what lies past d_msg_len[i] in there is
+ * undefined), so a buffer may end where the next begins, at any alignment.
+ * d_pos changes only by the two rules above.  d_wire is not modified, d_out
+ * only by the frame pass.
+ *
+ * d_work: bpmd_receive_takeover_work_bytes(n) (host only) bytes of device
+ * memory the call may overwrite: bpmd_receive_batch's arrays, then per entry
+ * the window length and the 64-bit output offset.  One workspace serves one
+ * call at a time.
+ *
+ * Everything is enqueued on `stream` and no step reads anything back: which
+ * connections slide is decided on the device.  Out of scope as for
+ * bpmd_receive_batch: more than one event per entry and call, partial frames.
+ * n == 0 is a no-op; BPMD_R_INVALID_ARGUMENT for a role that is neither
+ * value, a NULL pointer other than d_state, BPMD_F_RAW, a NULL cfg or
+ * slot_bytes <= 2 * W; BPMD_R_DOMAIN_ERROR for window bits outside 8..15;
+ * BPMD_R_NO_DEVICE without a GPU. */
+size_t bpmd_receive_takeover_work_bytes(uint32_t n);
+int bpmd_receive_takeover_batch(const bpmd_cfg* cfg, int role, uint64_t msg_max, const uint8_t* d_wire,
+                                const uint64_t* d_wire_off, const uint32_t* d_wire_len, uint32_t n,
+                                bpmd_rd_state* d_state, uint8_t* d_out, const uint64_t* d_out_off,
+                                const uint32_t* d_out_cap, uint32_t* d_out_len, uint8_t* d_op, uint8_t* d_compressed,
+                                uint8_t* d_event, int32_t* d_status, uint32_t* d_consumed, uint8_t* d_ctl,
+                                uint8_t* d_ctl_len, uint16_t* d_close_code, uint8_t* d_buf, const uint64_t* d_base,
+                                uint32_t slot_bytes, uint32_t* d_pos, const uint32_t* d_msg_cap, uint64_t* d_msg_off,
+                                uint32_t* d_msg_len, void* d_work, void* stream);
 
 /* ---------------------------------------------------------------------
  * Per-stream API behind the C++ compatibility facade
