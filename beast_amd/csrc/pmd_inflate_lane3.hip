@@ -38,6 +38,33 @@
 // Token word 1: bits 0-2 literal count, 3-11 match length (0 = none),
 // 12-27 distance; bit 31 = END (word 0 = out_len, bits 0-7 = status).
 // Output semantics per message are those of pmd_inflate.hip.
+//
+// Output checks (byte path, BPMD3_XCHK=1): the decoder makes the input-side
+// checks of a symbol (starved input, invalid codes, end of block) and sends
+// every decodable token whole; it reads neither the capacity nor the history
+// in its data step.  The expander, which tracks pos, cap and hist anyway,
+// applies the reference's output checks to each token it takes, in the
+// reference's order (inflate_stream.ipp:475-514): a full output (first in raw
+// framing), a distance before the window, a full output, a cut match.  On a
+// failing token it emits the part that fits, writes the message's out_len
+// and status itself and STOPS the message:
+//   expander  stores tail | TAIL_STOP (bit 31 of the tail word; ring
+//             arithmetic masks it), and drops every later token of the
+//             message up to and including its END token, whose payload it
+//             ignores; the tail store that takes the END clears the bit
+//   decoder   reads the tail word every iteration; a lane whose bit is set
+//             goes to S_DONE, result untouched, and still sends its END (the
+//             queue protocol and the loop's exit need it)
+//   NEW       (work queue) is published only when the tail word equals head
+//             with the bit clear: the expander has then taken the END before
+//             it, so the bit cannot belong to, or later be raised by, the
+//             message before
+// Tokens are taken in stream order, so the first failing token of the stream
+// decides, as in the serial reference: an input-side error the decoder met
+// earlier ends the stream before the failing token is ever sent; one it meets
+// later, running ahead, arrives as an END after the stop and is dropped.
+// The decoder's pos can run past cap between an overflowing token and the
+// stop; only the stored-block copy reads it, and cuts to nothing there.
 #include <hipcub/hipcub.hpp>
 
 #include "pmd_common.h"
@@ -92,6 +119,15 @@ constexpr uint32_t TOK_STORED = 0x10000000u;  // segment mode: bits 0-15 stored 
 #define BPMD3_XPIPE 0
 #endif
 constexpr int KX = BPMD3_KX;   // expander pieces per iteration
+// BPMD3_XCHK=1: the expander applies the output checks of a data token and
+// stops the message (see "Output checks" in the header comment); 0: the
+// decoder does, as before (the A/B parent).  The byte path only: segment
+// mode keeps its checks in the decoder.
+#ifndef BPMD3_XCHK
+#define BPMD3_XCHK 1
+#endif
+constexpr uint32_t TAIL_STOP = 0x80000000u;   // W_TAIL bit 31: the expander has stopped the lane's message
+constexpr uint32_t TAIL_MASK = 0x7fffffffu;
 #ifndef BPMD3_DPRIO
 #define BPMD3_DPRIO 3
 #endif
@@ -191,7 +227,15 @@ __device__ unsigned long long g_l3prof[16];
 // TABLE + LENLENS, CODELENS, BUILD, PLACE), [5-7] per-task records; [7] bits
 // 40-63: lane-headers whose run list did not fit (prof build only)
 __device__ unsigned long long g_l3hprof[8];
+// the byte expander's cycles per wave, summed (prof build only): [0] from the
+// loop's top until s_waitcnt vmcnt(0) returns: the chunks loaded in the
+// iteration before have arrived and its stores have completed too, so an
+// upper bound of the exposed load round trip, [1] the stores, [2] taking pieces,
+// [3] the rest (exit and sleep tests, sleeps)
+__device__ unsigned long long g_l3xprof[4];
 #ifdef BPMD_PROF
+#define L3_XWAIT() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
+#define L3_XLAPFLUSH() do { if ((threadIdx.x & 63) == 0) for (int i_ = 0; i_ < 4; ++i_) atomicAdd(&g_l3xprof[i_], l3lap_[i_]); } while (0)
 #define L3_DECL unsigned long long l3t0_ = __builtin_amdgcn_s_memtime(), l3c_[4] = {0, 0, 0, 0}
 #define L3_CNT(i) (l3c_[i] += 1)
 #define L3_LAPDECL unsigned long long l3l_ = __builtin_amdgcn_s_memtime(), l3lap_[4] = {0, 0, 0, 0}
@@ -209,6 +253,8 @@ __device__ unsigned long long g_l3hprof[8];
 #define L3_LAPDECL
 #define L3_LAP(i)
 #define L3_LAPFLUSH()
+#define L3_XWAIT()
+#define L3_XLAPFLUSH()
 #define L3_HSTART()
 #define L3_HLAP(i)
 #endif
@@ -227,8 +273,11 @@ static __constant__ const uint8_t kClenOrder2[19] = {16, 17, 18, 0, 8, 7, 9, 6, 
 __device__ __forceinline__ void expander(uint8_t* T, bool valid, uint32_t m, uint8_t* __restrict__ out,
                                          const uint64_t* __restrict__ out_off, const uint32_t* __restrict__ out_cap,
                                          uint32_t* __restrict__ out_len, int32_t* __restrict__ status,
-                                         const uint32_t* __restrict__ hist_len, uint32_t hist_max, bool queue)
+                                         const uint32_t* __restrict__ hist_len, uint32_t hist_max, bool queue,
+                                         uint32_t raw)
 {
+    const int32_t full_status = raw ? ST_OK : ST_NEED_BUFFERS;
+    bool stopped = false;   // BPMD3_XCHK: this message has its result; its tokens up to END are dropped
     uint8_t* o = out;
     uint32_t cap = 0, hist = 0;
     auto slot = [&](uint32_t mm) {
@@ -252,6 +301,7 @@ __device__ __forceinline__ void expander(uint8_t* T, bool valid, uint32_t m, uin
         m_w[j] = make_uint4(0, 0, 0, 0);
     }
     L3_DECL;
+    L3_LAPDECL;
     for (;;) {
         bool pending = false;
 #pragma unroll
@@ -259,6 +309,9 @@ __device__ __forceinline__ void expander(uint8_t* T, bool valid, uint32_t m, uin
         if (!__ballot(!exited || crem != 0 || pending)) break;
         L3_CNT(1);
         bool worked = pending;
+        L3_LAP(3);
+        L3_XWAIT();
+        L3_LAP(0);
         // ================================================ stores, output order
         // (a store's bytes past its piece are overwritten by the next one)
 #pragma unroll
@@ -295,6 +348,7 @@ __device__ __forceinline__ void expander(uint8_t* T, bool valid, uint32_t m, uin
             m_sz[j] = 0;
             m_pat[j] = 0;
         }
+        L3_LAP(1);
         // ================================================ take pieces
         if (!exited) {
             const uint32_t head = lds_load((uint8_t*)lw(T, W_HEAD));
@@ -316,9 +370,12 @@ __device__ __forceinline__ void expander(uint8_t* T, bool valid, uint32_t m, uin
 #pragma unroll
                         for (int i = 1; i <= j; ++i) e = pick(e, ent[i], k == (uint32_t)i);
                         if (e.y & TOK_END) {
-                            out_len[m] = e.x;
-                            const int32_t stt = (int32_t)(int8_t)(e.y & 0xffu);
-                            status[m] = stt;
+                            if (!stopped) {
+                                out_len[m] = e.x;
+                                const int32_t stt = (int32_t)(int8_t)(e.y & 0xffu);
+                                status[m] = stt;
+                            }
+                            stopped = false;   // the tail store below clears the stop bit
                             exited = !queue;
                             ++tail;
                             ++k;
@@ -339,20 +396,52 @@ __device__ __forceinline__ void expander(uint8_t* T, bool valid, uint32_t m, uin
                                 worked = true;
                             }
                             stop = true;
+                        } else if (BPMD3_XCHK && stopped) {
+                            // a token the decoder sent before it saw the stop bit
+                            ++tail;
+                            ++k;
+                            worked = true;
                         } else {
-                            const uint32_t nl = e.y & 7u, ml = (e.y >> 3) & 511u;
+                            uint32_t nl = e.y & 7u, ml = (e.y >> 3) & 511u;
+                            const uint32_t dist = (e.y >> 12) & 0xffffu;
+                            bool halt = false;
+                            int32_t hst = full_status;
+                            if (BPMD3_XCHK) {
+                                // the literals, one output byte each (pos <= cap here)
+                                const uint32_t left = cap - pos;
+                                halt = nl > left;
+                                nl = halt ? left : nl;
+                                ml = halt ? 0u : ml;
+                            }
                             if (nl) {
                                 l_dst[j] = pos;
                                 l_val[j] = e.x;
                                 l_n[j] = nl;
                                 pos += nl;
                             }
+                            if (BPMD3_XCHK && ml) {
+                                // the match, in the reference's order (inflate_stream.ipp:475-514):
+                                // raw mode's full output, the distance, the full output, the cut
+                                const bool c_full = pos >= cap, c_dist = dist > pos + hist;
+                                const bool s_full = c_full && (raw != 0 || !c_dist);
+                                const bool s_dist = !s_full && c_dist;
+                                const bool c_trunc = pos + ml > cap;
+                                halt = s_full || s_dist || c_trunc;
+                                hst = s_dist ? (int32_t)ST_INVALID_DISTANCE : full_status;
+                                ml = (s_full || s_dist) ? 0u : c_trunc ? cap - pos : ml;
+                            }
                             if (ml) {
                                 crem = ml;
-                                cdist = (e.y >> 12) & 0xffffu;
+                                cdist = dist;
                                 cq = pos;
                                 cpat_st = 0;
                                 pos += ml;
+                            }
+                            if (BPMD3_XCHK && halt) {
+                                // the message's result; the pieces taken so far are still stored
+                                out_len[m] = pos;
+                                status[m] = hst;
+                                stopped = true;
                             }
                             ++tail;
                             ++k;
@@ -410,14 +499,16 @@ __device__ __forceinline__ void expander(uint8_t* T, bool valid, uint32_t m, uin
                     }
                 }
             }
-            lds_store((uint8_t*)lw(T, W_TAIL), tail);
+            lds_store((uint8_t*)lw(T, W_TAIL), BPMD3_XCHK ? (tail & TAIL_MASK) | (stopped ? TAIL_STOP : 0u) : tail);
         }
+        L3_LAP(2);
         if (!__ballot(worked)) {   // the decoder is behind: leave it the SIMD
             L3_CNT(2);
             __builtin_amdgcn_s_sleep(BPMD3_ESLEEP);
         }
     }
     L3_FLUSH(4);
+    L3_XLAPFLUSH();
 }
 
 // --------------------------------------------------------- segment expander
@@ -733,6 +824,7 @@ __device__ __forceinline__ void decoder(uint8_t* T, bool valid, uint32_t m, cons
                                         uint32_t* __restrict__ qctr, uint32_t s0,
                                         const bp::SegTask* __restrict__ tasks)
 {
+    constexpr bool XC = !SEG && BPMD3_XCHK != 0;   // the expander makes the output checks
     const uint32_t tail = raw ? 0u : 4u;
     const int32_t full_status = SEG ? bp::SEG_FULL : raw ? ST_OK : ST_NEED_BUFFERS;
     // segment mode: payload bit of the view's first bit, the view's bits, and
@@ -899,7 +991,7 @@ __device__ __forceinline__ void decoder(uint8_t* T, bool valid, uint32_t m, cons
             mk = mask_key ? __builtin_amdgcn_alignbit(mask_key[mm], mask_key[mm], 8u * ((0u - s_) & 3u)) : 0u;
             // context takeover (bpmd_inflate_takeover_batch): the hist bytes before
             // the slot are the window Beast's inflater keeps across messages
-            hist = hist_len ? (hist_len[mm] < hist_max ? hist_len[mm] : hist_max) : 0u;
+            if (!XC) hist = hist_len ? (hist_len[mm] < hist_max ? hist_len[mm] : hist_max) : 0u;
             open_view(p, in_len[mm] - byte0);
         }
         drop(8 * s + bit0);
@@ -976,7 +1068,7 @@ __device__ __forceinline__ void decoder(uint8_t* T, bool valid, uint32_t m, cons
         // registers, so their KLIT symbol lookups go out together.
         refill();   // nb >= 33: with q.x, a 64-bit window
         const uint64_t w = nb >= 64 ? bb : (bb | ((uint64_t)q.x << nb));
-        const bool multi = (tb + (int32_t)nb) >= 48 + 15 * (KLIT - 1) && pos + KLIT <= cap;
+        const bool multi = (tb + (int32_t)nb) >= 48 + 15 * (KLIT - 1) && (XC || pos + KLIT <= cap);
         uint32_t kp[KLIT + 1], kc[KLIT], kL[KLIT], kx[KLIT];
         bool kinv[KLIT];
         kp[0] = 0;
@@ -1075,8 +1167,19 @@ __device__ __forceinline__ void decoder(uint8_t* T, bool valid, uint32_t m, cons
         const int32_t err = inval ? ST_INVALID_LITERAL_LENGTH : ST_INVALID_DISTANCE_CODE;
         const bool is_match = ev == 0 && is_len;
         drop_x(mt && ev < 2 ? (is_match ? used + Ld + xd : used) : 0u);
-        // output checks in the reference's order (inflate_stream.ipp:475-514)
         const bool tok = mt && ev == 0;
+        if (XC) {
+            // the token goes out whole: the expander checks it against the output
+            result = (mt && ev == 3) ? err : result;
+            st = (mt && ev >= 2) ? (uint32_t)S_DONE : (mt && ev == 1) ? (uint32_t)S_TYPE : st;
+            emlen = tok && is_len ? len : 0u;
+            edist = tok && is_len ? dist : 0u;
+            enl = tok && !is_len ? 1u : enl;
+            elit = tok && !is_len ? sym : elit;
+            pos += tok ? (is_len ? len : 1u) : 0u;
+            return;
+        }
+        // output checks in the reference's order (inflate_stream.ipp:475-514)
         const bool c_raw = !SEG && raw && pos >= cap;
         const bool c_dist = !SEG && is_match && dist > pos + hist;
         const bool c_full = pos >= cap;
@@ -1133,10 +1236,15 @@ __device__ __forceinline__ void decoder(uint8_t* T, bool valid, uint32_t m, cons
 #endif
         // ---- the input pipeline (the only global memory the decoder touches)
         if (nx_used) pipe();
-        const uint32_t taken = lds_load((uint8_t*)lw(T, W_TAIL));
+        const uint32_t tailw = lds_load((uint8_t*)lw(T, W_TAIL));
         compiler_fence();
-        const bool room = head - taken < RING;
-        const bool ring_empty = head == taken;
+        const uint32_t taken = XC ? tailw & TAIL_MASK : tailw;
+        const uint32_t queued = XC ? (head - taken) & TAIL_MASK : head - taken;
+        const bool room = queued < RING;
+        const bool ring_empty = queued == 0;
+        // the expander has stopped this message: nothing more is decoded, the
+        // END token still goes out (the expander drops everything up to it)
+        if (XC && (tailw & TAIL_STOP) && !fin) st = S_DONE;
 #ifdef BPMD_PROF
         // lane states per iteration: [12] data lanes blocked by a full ring,
         // [13] data lanes with room, [14] finished lanes, [15] header lanes
@@ -1267,7 +1375,8 @@ __device__ __forceinline__ void decoder(uint8_t* T, bool valid, uint32_t m, cons
                     uint32_t nc = v < have_b ? v : have_b;
                     sfull = false;
                     if (pos + nc > cap) {
-                        nc = cap - pos;
+                        // (pos is past cap only while a stop of the expander is on its way)
+                        nc = !XC || pos < cap ? cap - pos : 0u;
                         sfull = true;
                     }
                     sstarve = nc < v;
@@ -1656,7 +1765,10 @@ __device__ __forceinline__ void decoder(uint8_t* T, bool valid, uint32_t m, cons
             const bool ctl = send_new || send_exit;       // NEW / EXIT (work queue)
             const bool data = !ctl && (enl || emlen || estored);   // produced only with room
             const bool endt = !ctl && !data && st == S_DONE && !fin;
-            const bool adv = room && (ctl || data || endt);
+            // NEW waits until the expander has taken the END before it: the stop
+            // bit is then clear and no token that could set it is in the ring
+            const bool hold = XC && send_new && (!ring_empty || (tailw & TAIL_STOP));
+            const bool adv = room && !hold && (ctl || data || endt);
             const uint32_t hand =
                 SEG && (result == bp::SEG_HANDOFF || result == bp::SEG_DIRECT) ? (nk - msg) << 8 : 0u;
             const uint2 ent = ctl    ? make_uint2(msg, send_new ? TOK_NEW : TOK_EXIT)
@@ -1694,9 +1806,10 @@ __device__ __forceinline__ void decoder(uint8_t* T, bool valid, uint32_t m, cons
 #pragma unroll
         for (int xs = 0; xs < BPMD3_XSTEPS; ++xs) {
             if (BPMD3_XPIPE && nx_used && st0 == S_DATA && st == S_DATA) pipe();
-            if (!__ballot(st0 == S_DATA && st == S_DATA && !nx_used && head - taken < RING)) break;
+            const bool room2 = (XC ? (head - taken) & TAIL_MASK : head - taken) < RING;
+            if (!__ballot(st0 == S_DATA && st == S_DATA && !nx_used && room2)) break;
             uint32_t enl2 = 0, elit2 = 0, emlen2 = 0, edist2 = 0;
-            if (st0 == S_DATA && st == S_DATA && !nx_used && head - taken < RING)
+            if (st0 == S_DATA && st == S_DATA && !nx_used && room2)
                 data_step(enl2, elit2, emlen2, edist2);
             const bool adv2 = enl2 != 0 || emlen2 != 0;
             if (adv2) ring_st(T, head, make_uint2(elit2, enl2 | (emlen2 << 3) | (edist2 << 12)));
@@ -1759,7 +1872,7 @@ inflate_lane3_kernel(const uint8_t* __restrict__ in, const uint64_t* __restrict_
         decoder<false>(T, valid, m, in, in_off, in_len, out_cap, raw, mask_key, hist_len, hist_max, n_msgs, order, qctr,
                        s0, nullptr);
     } else {
-        expander(T, valid, m, out, out_off, out_cap, out_len, status, hist_len, hist_max, qctr != nullptr);
+        expander(T, valid, m, out, out_off, out_cap, out_len, status, hist_len, hist_max, qctr != nullptr, raw);
     }
 }
 
@@ -1960,3 +2073,14 @@ static int lane3_counters(unsigned long long* out, int reset, int n24)
 }
 extern "C" int bpmd_diag_lane3_counters(unsigned long long* out16, int reset) { return lane3_counters(out16, reset, 0); }
 extern "C" int bpmd_diag_lane3_counters24(unsigned long long* out24, int reset) { return lane3_counters(out24, reset, 1); }
+// the byte expander's laps (g_l3xprof, prof build)
+extern "C" int bpmd_diag_lane3_xlaps(unsigned long long* out4, int reset)
+{
+    hipError_t e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpyFromSymbol(out4, HIP_SYMBOL(bpmd::lp3::g_l3xprof), sizeof(unsigned long long) * 4);
+    if (e == hipSuccess && reset) {
+        unsigned long long z[4] = {0};
+        e = hipMemcpyToSymbol(HIP_SYMBOL(bpmd::lp3::g_l3xprof), z, sizeof z);
+    }
+    return (int)e;
+}

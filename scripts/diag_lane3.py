@@ -29,9 +29,12 @@ def main():
     pmd.inflate_batch(src, cap)
     torch.cuda.synchronize()
     L.bpmd_diag_lane3_counters24(c, 1)
+    x = (ctypes.c_ulonglong * 4)()
+    L.bpmd_diag_lane3_xlaps(x, 1)
     r = pmd.inflate_batch(src, cap)
     torch.cuda.synchronize()
     L.bpmd_diag_lane3_counters24(c, 1)
+    L.bpmd_diag_lane3_xlaps(x, 1)
     ok = torch.equal(r.out.data[: n * size].view(n, size), torch.from_numpy(raw.reshape(n, size)).to(dev))
     w = n // 64
     names = ["dec cycles", "dec iters", "dec sleeps", "dec hdr iters", "exp cycles", "exp iters", "exp sleeps", "lanes: header, ring not empty",
@@ -45,6 +48,10 @@ def main():
     # g_l3hprof[7]: bits 40-63 count the lane-headers whose run list did not
     # fit and that took the walk over every symbol (hdr_list.h)
     print(f"{'hdr: placed by the symbol walk':14s} {c[23] >> 40:12d} lane-headers")
+    # the expander's iteration: waiting for the chunks loaded in the iteration
+    # before, storing them, taking the next pieces, and the rest
+    for i, nm in enumerate(["exp lap: wait for loads", "exp lap: stores", "exp lap: take pieces", "exp lap: tests+sleep"]):
+        print(f"{nm:14s} {x[i] / w:12.0f} per wave")
     print("exact", ok)
 
 
