@@ -360,7 +360,10 @@ int inflate_impl(const bpmd_cfg* cfg, const Batch& b, const uint32_t* key, const
     return e ? BPMD_R_HIP_ERROR : BPMD_R_OK;
 }
 
-int deflate_impl(const bpmd_cfg* cfg, const Batch& b, const uint32_t* key, const uint32_t* hist, void* stream)
+// chunk_bound >= 0 (with hist): at least the batch's chunk count, so the
+// deflater does not read it back (bpmd::deflate_takeover_bounded)
+int deflate_impl(const bpmd_cfg* cfg, const Batch& b, const uint32_t* key, const uint32_t* hist, void* stream,
+                 int64_t chunk_bound = -1)
 {
     if (!cfg) return BPMD_R_INVALID_ARGUMENT;
     // deflate_stream.ipp:235-253: level -1 means 6; windowBits 8 becomes 9;
@@ -384,7 +387,7 @@ int deflate_impl(const bpmd_cfg* cfg, const Batch& b, const uint32_t* key, const
         if (hist) return BPMD_R_INVALID_ARGUMENT;
         return deflate_exact(b, level, wbits, cfg->mem_level, cfg->strategy, key, s) ? BPMD_R_HIP_ERROR : BPMD_R_OK;
     }
-    int e = hist ? deflate_takeover(b, level, wbits, cfg->strategy, hist, s)
+    int e = hist ? deflate_takeover(b, level, wbits, cfg->strategy, hist, s, chunk_bound)
                  : deflate_keyed(b, level, wbits, cfg->strategy, key, s);
     return e ? BPMD_R_HIP_ERROR : BPMD_R_OK;
 }
@@ -526,6 +529,13 @@ extern "C" int bpmd_deflate_takeover_batch(const bpmd_cfg* cfg, const uint8_t* d
     const Batch b{d_in, d_in_off, d_in_len, n_msgs, d_out, d_out_off, d_out_cap, d_out_len, d_status};
     if (n_msgs && !d_hist_len) return BPMD_R_INVALID_ARGUMENT;
     return deflate_impl(cfg, b, nullptr, d_hist_len, stream);
+}
+
+int bpmd::deflate_takeover_bounded(const bpmd_cfg* cfg, const Batch& b, const uint32_t* hist_len, uint64_t chunk_bound,
+                                   hipStream_t stream)
+{
+    if ((b.n && !hist_len) || chunk_bound > 0xFFFFFFFFull) return BPMD_R_INVALID_ARGUMENT;
+    return deflate_impl(cfg, b, nullptr, hist_len, stream, (int64_t)chunk_bound);
 }
 
 extern "C" int bpmd_slide_batch(uint8_t* d_buf, const uint64_t* d_base, const uint32_t* d_pos, const uint32_t* d_keep,

@@ -1702,9 +1702,15 @@ namespace {
 // max_chain) (deflate_stream.ipp:307-317) replacing the level's table row;
 // the level still picks the parser, and the chain keeps the engine's caps
 // host_chunks >= 0: the caller knows the batch's chunk count (the per-stream
-// deflater, one message of known length), so nothing is read back
+// deflater, one message of known length: exact_chunks) or a bound on it (the
+// chained takeover send, n * ceil(L / 4096)), so nothing is read back.  The
+// host value lays out the workspace and caps the chunk kernel's grid; the
+// kernels take the count itself from d_total on the device, so any value at
+// least the count serves, except on the one-message path, whose setup kernel
+// writes the host value as the count.
 int deflate_impl(const bpmd::Batch& b, uint32_t* out_bits, const uint32_t* mask_key, const uint32_t* hist_len, int level,
-                 int window_bits, int strategy, hipStream_t stream, const int* tune = nullptr, int64_t host_chunks = -1)
+                 int window_bits, int strategy, hipStream_t stream, const int* tune = nullptr, int64_t host_chunks = -1,
+                 bool exact_chunks = true)
 {
     const auto& [in, in_off, in_len, n, out, out_off, out_cap, out_len, status] = b;
     bpmd::dfl::Params P;
@@ -1735,7 +1741,7 @@ int deflate_impl(const bpmd::Batch& b, uint32_t* out_bits, const uint32_t* mask_
     if (!d_total) return (int)hipErrorOutOfMemory;
     // one message with its chunk count known (a stream's write): one setup
     // launch below instead of the memset, the count, the scan and the fill
-    const bool one = n == 1 && host_chunks >= 0;
+    const bool one = n == 1 && host_chunks >= 0 && exact_chunks;
     hipError_t he = hipSuccess;
     if (!one) {
         he = hipMemsetAsync(d_total, 0, 256, stream);
@@ -1747,7 +1753,7 @@ int deflate_impl(const bpmd::Batch& b, uint32_t* out_bits, const uint32_t* mask_
     P.chain = chain(true);
     if (host_chunks >= 0) {
         if (host_chunks > 0xFFFFFFFFll) return (int)hipErrorInvalidValue;
-        total = (uint32_t)host_chunks;   // the device count above is the same number
+        total = (uint32_t)host_chunks;   // the device count above is this number or less
         const int e = all ? 0 : launch_single(b, P, stream);
         if (e) return e;
     } else {
@@ -1775,6 +1781,7 @@ int deflate_impl(const bpmd::Batch& b, uint32_t* out_bits, const uint32_t* mask_
         return 0;
     }
     // workspace: first[n + 1] | items[total] | bits[total] | slots[total] | scan temp
+    // (total: the count, or the caller's bound on it)
     // (round 5's single-write chunk kernel, which placed each chunk's block
     // without the stitch's second write, measured slower -- a chunk's wave
     // waits, holding its CU slot, for the chunk before it to finish encoding:
@@ -1853,9 +1860,9 @@ int bpmd::deflate_keyed(const Batch& b, int level, int window_bits, int strategy
 }
 
 int bpmd::deflate_takeover(const Batch& b, int level, int window_bits, int strategy, const uint32_t* hist_len,
-                           hipStream_t stream)
+                           hipStream_t stream, int64_t chunk_bound)
 {
-    return deflate_impl(b, nullptr, nullptr, hist_len, level, window_bits, strategy, stream);
+    return deflate_impl(b, nullptr, nullptr, hist_len, level, window_bits, strategy, stream, nullptr, chunk_bound, false);
 }
 
 extern "C" int bpmd_diag_deflate_counters(unsigned long long* out, int reset)

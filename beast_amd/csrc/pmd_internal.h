@@ -10,9 +10,12 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include <functional>
 #include <mutex>
 
 #include "bp.h"
+
+struct bpmd_cfg;   // include/beast_pmd.h
 
 namespace bpmd {
 
@@ -80,6 +83,41 @@ uint8_t* scratch_block(hipStream_t s, size_t bytes, ScratchSlot which);
 void* pinned_block(hipStream_t s, size_t bytes, PinnedSlot which);
 std::mutex* stream_mutex(hipStream_t s);
 
+// bpmd_deflate_takeover_batch without its wait: chunk_bound is at least the
+// batch's chunk count (at most 2^32 - 1), so the count is not read back and
+// the call only enqueues.  Checks cfg and takes the stream's launch lock as
+// the public call does.
+int deflate_takeover_bounded(const bpmd_cfg* cfg, const Batch& b, const uint32_t* hist_len, uint64_t chunk_bound,
+                             hipStream_t stream);
+
+// ---- pmd_send.hip: the send side's scan and frame launch, shared by
+// bpmd_send_batch and bpmd_send_takeover_batch.  launch_size enqueues the
+// caller's size kernel, which fills sizes[n] (0 = not sent) and the status so
+// far; then the 64-bit exclusive sum into wire_off and send_frame_kernel.
+// Takes the stream's launch lock.
+struct SendFrames {
+    const uint8_t* in;
+    const uint64_t* in_off;
+    const uint32_t* in_len;
+    uint32_t n;
+    bool masked, frag;
+    uint32_t frame_max;
+    const uint8_t* op;
+    const uint8_t* z;
+    const uint64_t* z_off;
+    const uint32_t* z_len;
+    const uint32_t* keys;
+    const uint32_t* key_base;
+    uint8_t* wire;
+    uint64_t wire_cap;
+    uint64_t* wire_off;
+    uint32_t* wire_len;
+    const uint8_t* compressed;
+    int32_t* status;
+    uint64_t* total;
+};
+int send_scan_frames(const SendFrames& a, const std::function<void(uint64_t* sizes)>& launch_size, hipStream_t s);
+
 // ---- pmd_inflate.hip: one wave per message
 int init_fixed();
 // min_in != 0: only payloads longer than min_in
@@ -104,10 +142,13 @@ int bp_reserve(hipStream_t s, unsigned long long in_bytes, unsigned long long ou
 // ---- pmd_deflate.hip, pmd_deflate_exact.hip
 int deflate_keyed(const Batch& b, int level, int window_bits, int strategy, const uint32_t* mask_key,
                   hipStream_t stream);
+// chunk_bound >= 0: at least the batch's chunk count (the sum of
+// deflate_chunks(len, true)); the chunk count is then not read back
 int deflate_takeover(const Batch& b, int level, int window_bits, int strategy, const uint32_t* hist_len,
-                     hipStream_t stream);
+                     hipStream_t stream, int64_t chunk_bound = -1);
 // the chunk count of one message of n bytes, with a history window or not:
-// the sum over a batch is deflate_bits_hist's host_chunks
+// deflate_bits_hist's host_chunks is the sum over its batch (for one message
+// exactly that; for more, that or any larger value)
 int64_t deflate_chunks(uint32_t n, bool hist);
 int deflate_bits_hist(const Batch& b, uint32_t* out_bits, const uint32_t* hist_len, int level, int window_bits,
                       int strategy, const int* tune, hipStream_t stream, int64_t host_chunks);

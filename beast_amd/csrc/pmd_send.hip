@@ -13,6 +13,8 @@
 //   3. send_size_kernel     each message's wire size and status;
 //   4. a 64-bit exclusive sum (hipCUB) of the sizes: the packed offsets;
 //   5. send_frame_kernel    headers and payloads, masked in client role.
+// Steps 4 and 5 behind a caller's own size kernel are send_scan_frames, which
+// bpmd_send_takeover_batch (pmd_send_takeover.hip) shares.
 // The deflater's length array lives in the caller's d_wire_len until step 3
 // overwrites it, so nothing of a call lives in the stream's shared scratch
 // while the stream's launch lock is released around step 2 (bpmd_deflate_batch
@@ -220,8 +222,24 @@ extern "C" int bpmd_internal_send_frames(const uint8_t* d_in, const uint64_t* d_
                                          uint32_t* d_wire_len, uint8_t* d_compressed, int32_t* d_status,
                                          uint64_t* d_total, void* stream)
 {
-    const hipStream_t s = (hipStream_t)stream;
     const bool masked = role == BPMD_ROLE_CLIENT;
+    const SendFrames a{d_in, d_in_off, d_in_len, n, masked, frag != 0, frame_max, d_op, d_z, d_z_off, d_z_len,
+                       masked ? d_keys : nullptr, d_key_base, d_wire, wire_cap, d_wire_off, d_wire_len, d_compressed,
+                       d_status, d_total};
+    const hipStream_t s = (hipStream_t)stream;
+    return send_scan_frames(
+        a,
+        [&](uint64_t* sizes) {
+            hipLaunchKernelGGL(send::send_size_kernel, dim3(elem_grid(n)), dim3(256), 0, s, d_in_len, d_z_len, d_op,
+                               d_compressed, have_z ? 1u : 0u, masked ? 1u : 0u, frag ? 1u : 0u, frame_max, n, d_status,
+                               sizes);
+        },
+        s);
+}
+
+int bpmd::send_scan_frames(const SendFrames& a, const std::function<void(uint64_t* sizes)>& launch_size, hipStream_t s)
+{
+    const uint32_t n = a.n;
     std::mutex* mu = stream_mutex(s);
     if (!mu) return BPMD_R_HIP_ERROR;
     std::lock_guard<std::mutex> launch(*mu);
@@ -233,15 +251,14 @@ extern "C" int bpmd_internal_send_frames(const uint8_t* d_in, const uint64_t* d_
     uint8_t* ws = scratch_block(s, o_cub + align256(cub_bytes ? cub_bytes : 1), SCR_SEND);
     if (!ws) return BPMD_R_HIP_ERROR;
     uint64_t* sizes = (uint64_t*)ws;
-    hipLaunchKernelGGL(send::send_size_kernel, dim3(elem_grid(n)), dim3(256), 0, s, d_in_len, d_z_len, d_op,
-                       d_compressed, have_z ? 1u : 0u, masked ? 1u : 0u, frag ? 1u : 0u, frame_max, n, d_status, sizes);
+    launch_size(sizes);
     if (hipGetLastError() != hipSuccess) return BPMD_R_HIP_ERROR;
-    if (hipcub::DeviceScan::ExclusiveSum(ws + o_cub, cub_bytes, (const uint64_t*)sizes, d_wire_off, (int)n, s) !=
+    if (hipcub::DeviceScan::ExclusiveSum(ws + o_cub, cub_bytes, (const uint64_t*)sizes, a.wire_off, (int)n, s) !=
         hipSuccess)
         return BPMD_R_HIP_ERROR;
-    hipLaunchKernelGGL(send::send_frame_kernel, dim3(wave_grid(n)), dim3(send::WAVE * send::WPB), 0, s, d_in, d_in_off,
-                       d_in_len, d_z, d_z_off, d_z_len, d_op, d_compressed, masked ? d_keys : nullptr, d_key_base,
-                       frag ? 1u : 0u, frame_max, n, sizes, d_wire, wire_cap, d_wire_off, d_wire_len, d_status, d_total);
+    hipLaunchKernelGGL(send::send_frame_kernel, dim3(wave_grid(n)), dim3(send::WAVE * send::WPB), 0, s, a.in, a.in_off,
+                       a.in_len, a.z, a.z_off, a.z_len, a.op, a.compressed, a.keys, a.key_base, a.frag ? 1u : 0u,
+                       a.frame_max, n, sizes, a.wire, a.wire_cap, a.wire_off, a.wire_len, a.status, a.total);
     return hipGetLastError() != hipSuccess ? BPMD_R_HIP_ERROR : BPMD_R_OK;
 }
 

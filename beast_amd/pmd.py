@@ -1163,6 +1163,103 @@ def send_batch(src: Batch, role: int, pmd_on: bool = True, threshold: int = 0, f
     return Sent(Batch(wire, w_off, w_len), status, comp, total, staging if pmd_on else None, key_base)
 
 
+def _send_tk_lib():
+    """_send_lib() with bpmd_send_takeover_batch's prototype, bound on first use"""
+    L = _send_lib()
+    if not getattr(L, "_send_tk_ready", False):
+        vp, u32, u64, ci = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int
+        L.bpmd_send_takeover_work_bytes.argtypes = [u32]
+        L.bpmd_send_takeover_work_bytes.restype = ctypes.c_size_t
+        L.bpmd_send_takeover_batch.argtypes = ([ctypes.POINTER(_Cfg), vp, vp, vp, u32, ci, u64, ci, u32, u32] + [vp] * 4
+                                               + [u32] + [vp] * 8 + [u64] + [vp] * 7)
+        L.bpmd_send_takeover_batch.restype = ci
+        L._send_tk_ready = True
+    return L
+
+
+class TakeoverSender:
+    """bpmd_send_takeover_batch over n_conn context-takeover connections:
+    send_batch's chained call (begin_msg's decision, deflater, frames, packed
+    wire) with TakeoverDeflater's buffers -- 2 * 4096 + max_msg bytes per
+    connection, a compressed message placed right behind the connection's
+    earlier compressed plaintext, the last 4 KiB slid to the front when a
+    message would not fit -- and that bookkeeping done on the device.  An
+    uncompressed message is framed straight from the caller's bytes and never
+    enters the history, as the peer's inflater never sees it.  Entry i of every
+    batch is connection i; op 0 marks a connection with nothing to send.  The
+    sender owns the connections' buffers (`buf`, `base`, `pos`), the staging
+    slots and the workspace; a Sent's tensors of one call are valid until the
+    next.  `max_msg` bounds every message, compressed or not: keys (client
+    role: `key_stride` per connection, frame f of connection i takes
+    keys[i * key_stride + f]) and the default wire are sized from it with
+    send_frame_bound / send_wire_bound.  A connection whose message came back
+    with need_buffers or WS_BUFFER_OVERFLOW has not advanced: send the message
+    again with more room, the others idle."""
+
+    HIST = 4096
+
+    def __init__(self, n_conn: int, role: int, level: int = 6, window_bits: int = 15, mem_level: int = 4,
+                 max_msg: int = 1 << 16, threshold: int = 0, frag: bool = True, frame_max: int = 4096, device="cuda"):
+        L = _send_tk_lib()
+        self.n, self.role, self.max_msg = n_conn, role, max_msg
+        self.threshold, self.frag, self.frame_max = threshold, frag, frame_max
+        self.cfg = _Cfg(level, window_bits, mem_level, 0, 0)
+        self.slot = (2 * self.HIST + max_msg + 15) // 16 * 16
+        self.buf = torch.zeros(n_conn * self.slot + 16, dtype=torch.uint8, device=device)
+        self.base = torch.arange(n_conn, dtype=torch.int64, device=device) * self.slot
+        self.pos = torch.zeros(n_conn, dtype=torch.int32, device=device)
+        masked = role == ROLE_CLIENT
+        self.key_stride = int(L.bpmd_send_frame_bound(max_msg, frame_max, 1, int(frag)))
+        self.wire_bound = int(L.bpmd_send_wire_bound(max_msg, frame_max, int(masked), 1, int(frag)))
+        self.key_base = (torch.arange(n_conn, dtype=torch.int32, device=device) * self.key_stride) if masked else None
+        zc = (upper_bound(max_msg) + 15) // 16 * 16
+        self.z = torch.empty(n_conn * zc + 16, dtype=torch.uint8, device=device)
+        self.z_off = torch.arange(n_conn, dtype=torch.int64, device=device) * zc
+        self.z_cap = torch.full((n_conn,), zc, dtype=torch.int32, device=device)
+        self.work = torch.empty(max(int(L.bpmd_send_takeover_work_bytes(n_conn)), 1), dtype=torch.uint8, device=device)
+
+    def send(self, src: Batch, op, opt=None, keys=None, wire: torch.Tensor | None = None, stream=None) -> Sent:
+        """One call over src (entry i: connection i's message).  `op`: 0 idle,
+        1 text, 2 binary, per connection or one value; `opt`: wr_compress_opt
+        per message (None = on).  Everything is enqueued on `stream`; with
+        `wire` given (wire_bound bytes per connection always suffice) the call
+        reads nothing back, without it the call also checks the lengths
+        against max_msg."""
+        L = _send_tk_lib()
+        dev = self.buf.device
+        n = src.n
+        if n != self.n:
+            raise BpmdError("TakeoverSender.send: one entry per connection")
+        masked = self.role == ROLE_CLIENT
+        kt = None
+        if masked:
+            if keys is None:
+                raise BpmdError("TakeoverSender.send: client role needs keys")
+            kt = _keys(keys, int(keys.numel()) if isinstance(keys, torch.Tensor) else len(keys), dev)
+            if kt.numel() < n * self.key_stride:
+                raise BpmdError("TakeoverSender.send: keys must hold key_stride keys per connection")
+        with _on(stream):
+            op_t, opt_t = _u8(op, n, dev), _u8(opt, n, dev)
+            if wire is None:
+                if n and int(src.len.max().item()) > self.max_msg:
+                    raise BpmdError("message exceeds max_msg")
+                wire = torch.empty(n * self.wire_bound + 16, dtype=torch.uint8, device=dev)
+            z_len = torch.zeros(n, dtype=torch.int32, device=dev)
+            w_off = torch.zeros(n, dtype=torch.int64, device=dev)
+            w_len = torch.zeros(n, dtype=torch.int32, device=dev)
+            comp = torch.zeros(n, dtype=torch.uint8, device=dev)
+            status = torch.zeros(n, dtype=torch.int32, device=dev)
+            total = torch.zeros(1, dtype=torch.int64, device=dev)
+        _check(L.bpmd_send_takeover_batch(
+            ctypes.byref(self.cfg), _ptr(src.data), _ptr(src.off), _ptr(src.len), n, self.role, self.threshold,
+            1 if self.frag else 0, self.frame_max, self.max_msg, _optr(op_t), _optr(opt_t), _ptr(self.buf),
+            _ptr(self.base), self.slot, _ptr(self.pos), _ptr(self.z), _ptr(self.z_off), _ptr(self.z_cap), _ptr(z_len),
+            _optr(kt), _optr(self.key_base), _ptr(wire), wire.numel(), _ptr(w_off), _ptr(w_len), _ptr(comp),
+            _ptr(status), _ptr(total), _ptr(self.work), _stream_handle(stream)), "bpmd_send_takeover_batch")
+        return Sent(Batch(wire, w_off, w_len), status, comp, total,
+                    Result(Batch(self.z, self.z_off, z_len), self.z_cap, status), self.key_base)
+
+
 @dataclass
 class Controls:
     wire: Batch            # one frame per entry at 144 * i; len 0 = refused

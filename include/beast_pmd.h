@@ -498,9 +498,9 @@ int bpmd_receive_batch(const bpmd_cfg* cfg, int role, int pmd_on, uint64_t msg_m
  * back; the one wait bpmd_deflate_batch has for messages over 4 KiB (its
  * chunk count, above) is inherited when such a message is compressed.
  * Until the call returns, d_wire_len holds the deflater's input lengths.
- * Deliberately out of scope: context-takeover sends
- * (bpmd_deflate_takeover_batch keeps its own layout) and a message that
- * arrives in several write_some pieces.
+ * Context-takeover sends have their own chained call,
+ * bpmd_send_takeover_batch (below).  Deliberately out of scope: a message
+ * that arrives in several write_some pieces.
  * n == 0 is a no-op; BPMD_R_INVALID_ARGUMENT for frame_max == 0, a role that
  * is neither value, client role without d_keys / d_key_base, a NULL required
  * pointer, or (pmd_on) a cfg bpmd_deflate_batch refuses; BPMD_R_NO_DEVICE
@@ -706,6 +706,85 @@ int bpmd_receive_takeover_batch(const bpmd_cfg* cfg, int role, uint64_t msg_max,
                                 uint8_t* d_ctl_len, uint16_t* d_close_code, uint8_t* d_buf, const uint64_t* d_base,
                                 uint32_t slot_bytes, uint32_t* d_pos, const uint32_t* d_msg_cap, uint64_t* d_msg_off,
                                 uint32_t* d_msg_len, void* d_work, void* stream);
+
+/* Decide, deflate with context takeover and frame a batch of connections in
+ * one chained call: bpmd_send_batch for connections whose deflater keeps its
+ * history (above), which is what Beast negotiates by default.  Entry i is
+ * connection i; a connection takes part in a call once.  pmd_on is implied.
+ *
+ * Everything not named here means what it means in bpmd_send_batch: d_in,
+ * d_in_off, d_in_len, role, threshold, frag, frame_max, d_opt, the staging
+ * slots d_z / d_z_off / d_z_cap / d_z_len, d_keys[d_key_base[i] + f], the
+ * packed wire with d_wire_off, d_wire_len and *d_total, d_compressed, and the
+ * guarantees about which wire bytes are written.  d_op[i] is 0 idle (nothing
+ * to send: status 0, size 0, the connection untouched, whatever the entry's
+ * other arrays hold), 1 text or 2 binary; NULL = all binary.
+ *
+ * K = 4096 is the plaintext a connection's buffer keeps; a match reaches at
+ * most BPMD_CHUNK_HIST (4096 at levels 7-9) bytes back, never more than K.
+ * Connection i owns the slot_bytes bytes at d_buf + d_base[i], of which the
+ * first d_pos[i] hold the messages it compressed last; d_pos is in/out, a new
+ * connection starts at 0 and d_pos[i] never exceeds slot_bytes.
+ * slot_bytes > 2 * K.  L = min(max_len, slot_bytes - 2 * K) is the longest
+ * message that can be compressed.
+ *   - Entry i is compressed iff d_op[i] is 1 or 2, d_opt[i] and d_in_len[i] >=
+ *     threshold (begin_msg); d_compressed[i] tells.  Such a message longer
+ *     than L gets BPMD_WS_MESSAGE_TOO_BIG and is not sent.  Otherwise, if
+ *     d_pos[i] + d_in_len[i] > slot_bytes, the K bytes before d_pos[i] are
+ *     first moved to the buffer's front and d_pos[i] becomes K (then d_pos[i]
+ *     was more than 2 * K, so the move never overlaps itself); the message is
+ *     copied to d_buf + d_base[i] + d_pos[i] and deflated there as
+ *     bpmd_deflate_takeover_batch does, with min(d_pos[i], K) bytes of
+ *     history, into its staging slot, and framed from there.
+ *     d_pos[i] advances by d_in_len[i] iff the final d_status[i] is 0, that
+ *     is, iff the message's frames are on the wire.  After BPMD_NEED_BUFFERS
+ *     or BPMD_WS_BUFFER_OVERFLOW the peer never saw the message, so the
+ *     history does not contain it: call again with the same message and a
+ *     larger staging slot or wire, and with d_op = 0 for the connections that
+ *     succeeded; the payload produced then is one the peer's window decodes.
+ *   - Every other entry leaves its connection alone: no slide, d_pos[i]
+ *     unchanged, no byte of its buffer written.  An uncompressed message is
+ *     framed straight from d_in and never enters the history, as it never
+ *     passes the peer's inflater; it may be longer than L.  Such entries reach
+ *     the deflater with length 0, which costs one byte of their staging slot
+ *     (a slot of 0 bytes is fine).
+ * d_status[i], by precedence: BPMD_WS_BAD_OPCODE (d_op[i] not 0, 1 or 2),
+ * BPMD_WS_MESSAGE_TOO_BIG, the deflater's BPMD_NEED_BUFFERS,
+ * BPMD_WS_BUFFER_OVERFLOW for the wire, 0.  An entry with one of the first
+ * three has size 0, like an idle one.
+ *
+ * The only bytes of d_buf written are, per entry, [d_base[i], d_base[i] + K)
+ * of a connection that slid and the message's own
+ * [d_base[i] + d_pos[i], ... + d_in_len[i]) of an entry that is deflated, so a
+ * buffer may end where the next begins, at any alignment.  d_pos changes only
+ * by the two rules above.  The frame step never reads d_buf.
+ *
+ * d_work: bpmd_send_takeover_work_bytes(n) (host only) bytes of device memory
+ * the call may overwrite: per entry the deflater's input length, its history,
+ * the status before it and the 64-bit input offset.  One workspace serves one
+ * call at a time.
+ *
+ * Everything is enqueued on `stream` and no step reads anything back: the
+ * deflater's chunk workspace (in the stream's scratch pool) is sized on the
+ * host for n * ceil(L / 4096) chunks instead of the batch's own count, so a
+ * caller whose messages are mostly short pays workspace for max_len; keep
+ * max_len near the longest message that is really compressed.  The only wait
+ * left is the stream's scratch pool growing on a stream's first calls.
+ * n == 0 is a no-op; BPMD_R_INVALID_ARGUMENT for frame_max == 0, a role that
+ * is neither value, a NULL required pointer (d_op, d_opt and, in server role,
+ * d_keys / d_key_base may be NULL), client role without d_keys / d_key_base,
+ * BPMD_F_EXACT or BPMD_F_RAW, slot_bytes <= 2 * K, max_len == 0,
+ * n * ceil(L / 4096) > 2^32 - 1, or a cfg bpmd_deflate_batch refuses;
+ * BPMD_R_NO_DEVICE without a GPU. */
+size_t bpmd_send_takeover_work_bytes(uint32_t n);
+int bpmd_send_takeover_batch(const bpmd_cfg* cfg, const uint8_t* d_in, const uint64_t* d_in_off,
+                             const uint32_t* d_in_len, uint32_t n, int role, uint64_t threshold, int frag,
+                             uint32_t frame_max, uint32_t max_len, const uint8_t* d_op, const uint8_t* d_opt,
+                             uint8_t* d_buf, const uint64_t* d_base, uint32_t slot_bytes, uint32_t* d_pos, uint8_t* d_z,
+                             const uint64_t* d_z_off, const uint32_t* d_z_cap, uint32_t* d_z_len,
+                             const uint32_t* d_keys, const uint32_t* d_key_base, uint8_t* d_wire, uint64_t wire_cap,
+                             uint64_t* d_wire_off, uint32_t* d_wire_len, uint8_t* d_compressed, int32_t* d_status,
+                             uint64_t* d_total, void* d_work, void* stream);
 
 /* ---------------------------------------------------------------------
  * Per-stream API behind the C++ compatibility facade
