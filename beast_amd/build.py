@@ -44,15 +44,30 @@ def _headers_mtime():
     return max(os.path.getmtime(h) for h in hs if os.path.exists(h))
 
 
+def _stale(obj: str, src: str, hmt: float, cmd) -> bool:
+    """True when `obj` must be recompiled: it is missing or older than its
+    source or the newest header (`hmt`), or the command line kept in
+    `<obj>.cmd` is missing or is not `cmd` (another set of -D flags)."""
+    if not os.path.exists(obj) or os.path.getmtime(obj) < max(os.path.getmtime(src), hmt):
+        return True
+    try:
+        with open(obj + ".cmd") as f:
+            return f.read() != "\n".join(cmd)
+    except OSError:
+        return True
+
+
 def _compile(src: str, hmt: float, bdir: str = BUILD, extra=()) -> str:
     obj = os.path.join(bdir, src.replace(".hip", ".o"))
     s = os.path.join(CSRC, src)
-    if os.path.exists(obj) and os.path.getmtime(obj) >= max(os.path.getmtime(s), hmt):
-        return obj
     cmd = [HIPCC, *CXXFLAGS, *SRC_FLAGS.get(src, []), *extra, "-c", s, "-o", obj]
+    if not _stale(obj, s, hmt, cmd):
+        return obj
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError(f"hipcc failed for {src}:\n{r.stderr}")
+    with open(obj + ".cmd", "w") as f:
+        f.write("\n".join(cmd))
     return obj
 
 

@@ -38,10 +38,9 @@ struct Sym {
     bool inval;
 };
 
-// NB words; BITS: the code width c is read at (the longest length, 15 for
-// literal/length and distance codes, 7 for the code-length code) -- equal to
-// NB except for the compact words below
-template <int NB, int BITS = NB>
+// c is read NB bits wide: the longest length (15 for literal/length and
+// distance codes, 7 for the code-length code)
+template <int NB>
 __device__ __forceinline__ Sym canon_decode(const uint32_t (&Q)[NB], uint32_t c)
 {
     const uint32_t m = canon_min<NB>(Q, c);
@@ -49,36 +48,9 @@ __device__ __forceinline__ Sym canon_decode(const uint32_t (&Q)[NB], uint32_t c)
     r.inval = (m >> 31) != 0;
     const uint32_t q = m + ((c + 1) << 15);
     r.L = (q >> 11) & 15u;
-    const int32_t below = (int32_t)(c - (q >> 15)) >> (BITS - (int32_t)r.L);   // in [-count_L, -1]
+    const int32_t below = (int32_t)(c - (q >> 15)) >> (NB - (int32_t)r.L);   // in [-count_L, -1]
     r.idx = r.inval ? 0u : (uint32_t)((int32_t)(q & 0x7ffu) + below);
     return r;
-}
-
-// A code uses few distinct lengths (deflated JSON: about 8-10 for
-// literal/length, 5-7 for distances), and a length with no codes adds a word
-// that can never win the search (its lim equals the length before it).  The
-// compact form keeps only the words of lengths that have codes, in order,
-// padded with 0 (0 - (c + 1) << 15 wraps above 2^31, so padding never wins
-// and an invalid code still reads as invalid): the same result as
-// canon_min<15> in K - 1 instead of 14 subtractions and mins.  Returns false
-// when the code has more than K distinct lengths (the caller keeps the full
-// search for it).
-template <int NB, int K>
-__device__ __forceinline__ bool compact_canon(const uint32_t (&Q)[NB], uint32_t (&W)[K])
-{
-    uint32_t rank = 0, prev = 0;
-#pragma unroll
-    for (int j = 0; j < K; ++j) W[j] = 0;
-#pragma unroll
-    for (int i = 0; i < NB; ++i) {
-        const uint32_t lim = Q[i] >> 15;
-        const bool used = lim != prev;
-        prev = lim;
-#pragma unroll
-        for (int j = 0; j < K; ++j) W[j] = (used && rank == (uint32_t)j) ? Q[i] : W[j];
-        rank += used ? 1u : 0u;
-    }
-    return rank <= (uint32_t)K;
 }
 
 // The reference's slow path asks for the root bits, or for root + sub-table

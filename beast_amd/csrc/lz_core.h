@@ -167,11 +167,9 @@ LZ_HD bool incompressible(unsigned hits, unsigned chunk_bytes)
 // stored block inflates as one copy: the block-parallel decoder takes it as a
 // single token and a lane never decodes it symbol by symbol -- C5's 8-way
 // shards were one Huffman chunk's serial decode.  Messages of one
-// chunk keep the size-based choice.  0 restores round 5's rule.
-#ifndef BPMD_INCOMP_STORED
-#define BPMD_INCOMP_STORED 1
-#endif
-constexpr bool INCOMP_STORED = BPMD_INCOMP_STORED != 0;
+// chunk keep the size-based choice.  (A constant, no switch: the kernel and
+// the host model of the tests both name the rule by it.)
+constexpr bool INCOMP_STORED = true;
 // Round 6: the block choice of a chunk of a multi-chunk message.  Beast keeps
 // a Huffman block whenever it is smaller than the stored one
 // (tr_flush_block, deflate_stream.ipp:1478: stored_len + 4 <= opt_lenb).
@@ -195,12 +193,7 @@ LZ_HD bool chunk_stored(unsigned clen, unsigned long long best_bytes, bool multi
 
 LZ_HD uint32_t chain_hash(uint32_t w, unsigned avail, unsigned hbits)
 {
-#ifdef BPMD_CHAIN_KEY3   // diagnostics: round 2's 3-byte keys
-    (void)avail;
-    return ((w & 0xFFFFFFu) * 0x9E3779B1u) >> (32 - hbits);
-#else
     return ((avail >= 4 ? w : (w & 0xFFFFFFu)) * 0x9E3779B1u) >> (32 - hbits);
-#endif
 }
 
 // ---------------------------------------------------------------- Huffman

@@ -59,15 +59,18 @@ constexpr unsigned HSIZE = 1u << HB;
 constexpr unsigned MIN_SEG = BPMD_MIN_SEG;   // parse segment floor (bytes per lane) of a chunk without history
 // A lane whose finds have walked more than BPMD_CHAIN_BUDGET chain candidates
 // per 64 bytes of its parse segment walks at most 4 per find from then on
-// (0 = no budget): the busiest lane sets a chunk's parse time
+// (0 = no budget: measured and left off; the prof build
+// compiles to other instructions without it, so it stays for now)
 #ifndef BPMD_CHAIN_BUDGET
 #define BPMD_CHAIN_BUDGET 0
 #endif
 // BPMD_DUAL_TEST: an iteration of the parse's chain walk that rejects its
 // candidate outright (no longer match, no byte run to extend) also tests the
-// next candidate of the chain, with the same limits and in the same order
-// (1), and in the chunk kernel (chain cap 32) a third after that (2; the
-// single-chunk kernel's walks are capped at 4 and lose with three)
+// next candidate of the chain, with the same limits and in the same order,
+// and in the chunk kernel (chain cap 32) a third after that (2; the
+// single-chunk kernel's walks are capped at 4 and lose with three), or a
+// fourth (3).  (The fourth lost, but the parse compiles to other
+// instructions without its dead form, so it stays for now.)
 // BPMD_MIN_SEG_HIST: the parse segment floor of a chunk with history bytes
 // before it (the host model's min_seg with history)
 #ifndef BPMD_MIN_SEG_HIST
@@ -586,29 +589,11 @@ __device__ void build_trees(HuffLds& H, Prof& pf)
         for (unsigned i = at + lane; i < P; i += WAVE) H.keys[i] = 0xFFFFFFFFu;
         wave_sync();
     }
-#ifdef BPMD_SORT_LDS   // diagnostics: round 3's bitonic sort through LDS
-    // --- bitonic sort of P keys (P / 128 compare-exchanges per lane per stage)
-    for (unsigned k = 2; k <= P; k <<= 1) {
-        for (unsigned j = k >> 1; j > 0; j >>= 1) {
-#pragma unroll
-            for (unsigned t = 0; t < 4; ++t) {
-                if (t >= P / 128) break;
-                const unsigned i = lane + t * WAVE;
-                const unsigned lo = ((i & ~(j - 1)) << 1) | (i & (j - 1)), hi = lo + j;
-                const uint32_t x = H.keys[lo], y = H.keys[hi];
-                const bool up = (lo & k) == 0;
-                if ((x > y) == up) { H.keys[lo] = y; H.keys[hi] = x; }
-            }
-            wave_sync();
-        }
-    }
-#else
     // --- bitonic sort of P keys in registers (P / 64 per lane)
     if (P == 128) sort_keys_reg<2>(H.keys);
     else if (P == 256) sort_keys_reg<4>(H.keys);
     else sort_keys_reg<8>(H.keys);
     wave_sync();
-#endif
     pf.lap(4);
     const unsigned ml = used_l, md = used_d;
     // a wide literal/length alphabet takes Shannon lengths (lz_core.h), no merge
@@ -860,21 +845,6 @@ __device__ void deflate_chunk(DefLds<HIST>& S, const uint8_t* msg, unsigned base
             // and dropped: hashes first into prev[], then four steps' LDS
             // atomics in flight together -- 573 K -> 653 K cycles per C4
             // message, profiles/r04x_diag_deflate_phases.log.)
-#ifdef BPMD_CHAIN1   // diagnostics: one step at a time
-            for (unsigned g = 0; g < wn; g += WAVE) {
-                const unsigned q = g + lane;
-                uint32_t pv = NONE;
-                if (q + MIN_MATCH <= wn) {
-                    const uint32_t h = chain_hash(W.dw(q), wn - q, HB);
-                    const uint32_t pre = S.b.head[h];
-                    const uint32_t old = atomicExch(&S.b.head[h], q);
-                    const uint32_t c = old < q ? old : pre;
-                    atomicMax(&S.b.head[h], q);
-                    pv = c < NONE ? c : NONE;
-                }
-                if (q < wn) S.a.prev[q] = (uint16_t)pv;
-            }
-#else
             // two steps per iteration: both steps' window loads and hashes
             // first, then their head operations in step order
             for (unsigned g = 0; g < wn; g += 2 * WAVE) {
@@ -900,7 +870,6 @@ __device__ void deflate_chunk(DefLds<HIST>& S, const uint8_t* msg, unsigned base
                 if (q0 < wn) S.a.prev[q0] = (uint16_t)pv0;
                 if (q1 < wn) S.a.prev[q1] = (uint16_t)pv1;
             }
-#endif
         }
         wave_sync();
         // incompressible chunk (near-random bytes): every INCOMP_STRIDE-th
@@ -982,7 +951,7 @@ __device__ void deflate_chunk(DefLds<HIST>& S, const uint8_t* msg, unsigned base
                 asm volatile("" : "+v"(h));   // one load for every lane, not a branch on rle
                 c = rle ? (q > 0 ? q - 1 : NONE) : h;
                 c = (no_match || q + MIN_MATCH > wn) ? NONE : c;
-                if (BPMD_DUAL_TEST) cn = S.a.prev[c < wn ? c : 0];
+                cn = S.a.prev[c < wn ? c : 0];
                 chain_left = rle ? 1u : (thr >= good ? chain_max >> 2 : chain_max);
                 if (BPMD_CHAIN_BUDGET) chain_left = steps > budget && chain_left > 4u ? 4u : chain_left;
                 nice = rle ? maxl : (nice_l < maxl ? nice_l : maxl);
@@ -990,7 +959,6 @@ __device__ void deflate_chunk(DefLds<HIST>& S, const uint8_t* msg, unsigned base
             setup();
             while (p < b) {
                 ++iters;
-#if BPMD_DUAL_TEST
                 // every load issued up front: candidate c, the next one cn (its
                 // prev cnn, and cnn's prev for an iteration that uses both)
                 const unsigned cc = c < wn ? c : 0, cc2 = cn < wn ? cn : 0;
@@ -1063,33 +1031,6 @@ __device__ void deflate_chunk(DefLds<HIST>& S, const uint8_t* msg, unsigned base
                 cn = adv4 ? c5 : (adv3 || go4) ? c4 : (adv2 || go3) ? cnnn : (adv1 || go2) ? cnn : cn;
                 c = c_new;
                 mt = go_match || ext || go2 || go3 || go4;
-#else
-                // every load issued up front
-                const unsigned cc = c < wn ? c : 0;
-                const uint32_t pn = S.a.prev[cc];
-                const uint32_t cb = W.byte(cc + best), qb = W.byte(q + best);
-                const uint64_t cv = W.qw(cc + l), qv = W.qw(q + l);
-                const unsigned k = eq_bytes(cv, qv);
-                const bool ch = !mt;
-                // bitwise, not short-circuit: no branches
-                const bool term = ch & ((c == NONE) | (q - c > max_dist) | (chain_left == 0));
-                const bool test = ch & !term;
-                const bool quick = test & (best < maxl) & (cb == qb) & (k > 0);
-                const bool go_match = quick & (k == 8) & (maxl > 8);
-                const bool ext = mt & (k == 8) & (l + 8 < maxl);
-                const bool have_len = (quick & !go_match) | (mt & !ext);
-                const unsigned len = l + k < maxl ? l + k : maxl;
-                const bool improve = have_len & (len > best);
-                best = improve ? len : best;
-                bd = improve ? q - c : bd;
-                const bool found = term | (improve & (len >= nice));
-                steps += test;
-                chain_left -= test;
-                const bool advance = !found & ((test & !go_match) | (mt & !ext));
-                l = go_match ? 8u : ext ? l + 8 : 0u;
-                c = advance ? pn : c;
-                mt = go_match || ext;
-#endif
                 if (found) {
                     // f_slow / f_fast decision, as selects
                     const bool drop = best > thr && best <= 5 &&
@@ -1671,13 +1612,9 @@ stitch_kernel(const uint32_t* __restrict__ in_len, uint32_t n, uint32_t all, con
 }  // namespace dfl
 }  // namespace bpmd
 
-#ifndef BPMD_DEFLATE_QUEUE
-#define BPMD_DEFLATE_QUEUE 1
-#endif
-
 namespace {
 // single-chunk messages: as many waves as the LDS holds, grid-strided or
-// (BPMD_DEFLATE_QUEUE) drained from a counter
+// (more messages than waves) drained from a counter
 int launch_single(const bpmd::Batch& b, const bpmd::dfl::Params& P, hipStream_t stream)
 {
     const uint32_t n = b.n;
@@ -1687,7 +1624,7 @@ int launch_single(const bpmd::Batch& b, const bpmd::dfl::Params& P, hipStream_t 
     if (bpmd_diag_grid_override) grid = bpmd_diag_grid_override;
     if (grid > n) grid = n;
     uint32_t* qctr = nullptr;
-    if (BPMD_DEFLATE_QUEUE && n > grid) {
+    if (n > grid) {
         qctr = (uint32_t*)bpmd::scratch_block(stream, 256, bpmd::SCR_DEFLATE_QUEUE);
         if (!qctr || hipMemsetAsync(qctr, 0, sizeof(uint32_t), stream) != hipSuccess) return (int)hipErrorOutOfMemory;
     }

@@ -1084,10 +1084,6 @@ inflate_kernel(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_o
 
 // ---------------------------------------------------------------- launcher
 
-#ifndef BPMD_WAVE_QUEUE
-#define BPMD_WAVE_QUEUE 1
-#endif
-
 // As many waves as the LDS holds (grid_override != 0: that many), each
 // taking its messages grid-strided or, with more messages than waves (or
 // always_queue), from a work queue.
@@ -1103,7 +1099,7 @@ static int launch_wave(const bpmd::Batch& b, uint32_t raw, const uint32_t* mask_
     if (grid_override) grid = grid_override;
     if (grid > b.n) grid = b.n;
     uint32_t* qctr = nullptr;
-    if (always_queue || (BPMD_WAVE_QUEUE && b.n > grid)) {
+    if (always_queue || b.n > grid) {
         qctr = (uint32_t*)scratch_block(stream, 256, SCR_WAVE_QUEUE);
         if (!qctr || hipMemsetAsync(qctr, 0, sizeof(uint32_t), stream) != hipSuccess) return (int)hipErrorOutOfMemory;
     }

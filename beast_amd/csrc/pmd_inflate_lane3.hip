@@ -39,10 +39,10 @@
 // 12-27 distance; bit 31 = END (word 0 = out_len, bits 0-7 = status).
 // Output semantics per message are those of pmd_inflate.hip.
 //
-// Output checks (byte path, BPMD3_XCHK=1): the decoder makes the input-side
-// checks of a symbol (starved input, invalid codes, end of block) and sends
-// every decodable token whole; it reads neither the capacity nor the history
-// in its data step.  The expander, which tracks pos, cap and hist anyway,
+// Output checks (byte path; segment mode keeps its checks in the decoder):
+// the decoder makes the input-side checks of a symbol (starved input, invalid
+// codes, end of block) and sends every decodable token whole; it reads
+// neither the capacity nor the history in its data step.  The expander, which tracks pos, cap and hist anyway,
 // applies the reference's output checks to each token it takes, in the
 // reference's order (inflate_stream.ipp:475-514): a full output (first in raw
 // framing), a distance before the window, a full output, a cut match.  On a
@@ -112,20 +112,7 @@ constexpr uint32_t TOK_STORED = 0x10000000u;  // segment mode: bits 0-15 stored 
 #ifndef BPMD3_KX
 #define BPMD3_KX 4
 #endif
-#ifndef BPMD3_XSTEPS
-#define BPMD3_XSTEPS 1
-#endif
-#ifndef BPMD3_XPIPE
-#define BPMD3_XPIPE 0
-#endif
 constexpr int KX = BPMD3_KX;   // expander pieces per iteration
-// BPMD3_XCHK=1: the expander applies the output checks of a data token and
-// stops the message (see "Output checks" in the header comment); 0: the
-// decoder does, as before (the A/B parent).  The byte path only: segment
-// mode keeps its checks in the decoder.
-#ifndef BPMD3_XCHK
-#define BPMD3_XCHK 1
-#endif
 constexpr uint32_t TAIL_STOP = 0x80000000u;   // W_TAIL bit 31: the expander has stopped the lane's message
 constexpr uint32_t TAIL_MASK = 0x7fffffffu;
 #ifndef BPMD3_DPRIO
@@ -135,29 +122,11 @@ constexpr int KLIT = BPMD3_KLIT;   // symbols decoded per iteration when literal
 #ifndef BPMD3_KCL
 #define BPMD3_KCL 6
 #endif
-// compact canonical search (canon.h compact_canon): words per literal/length
-// and distance table (0, the default: the full 15-word search only).
-// Measured slower on C2 (11 / 8 words: 163-167, 9 / 7: 172, off: 190-191
-// GiB/s, three interleaved runs, profiles/r05j_ab_compact_canon.log): the
-// compact words are 27 more VGPRs live across the loop (208 vs 181) and a
-// wave-uniform branch per decode, which cost more than the 9 subtractions
-// and mins they save.
-#ifndef BPMD3_CKL
-#define BPMD3_CKL 0
-#endif
-#ifndef BPMD3_CKD
-#define BPMD3_CKD 8
-#endif
-constexpr int CKL = BPMD3_CKL > 0 ? BPMD3_CKL : 1, CKD = BPMD3_CKD > 0 ? BPMD3_CKD : 1;
 constexpr int KCL = BPMD3_KCL;   // code-length symbols per iteration (pass 1; a refill before each, <= 4 input dwords per iteration)
 #ifndef BPMD3_KNIB
 #define BPMD3_KNIB 32
 #endif
 constexpr int KNIB = BPMD3_KNIB;  // code lengths placed per iteration (pass 2, nibble walk; a multiple of 8, at most 32)
-// BPMD3_PLIST=0: every header takes the nibble walk (the A/B arm of the list)
-#ifndef BPMD3_PLIST
-#define BPMD3_PLIST 1
-#endif
 constexpr uint32_t PL = 16;   // coded runs placed per iteration (pass 2, list walk)
 constexpr uint32_t DUMP = O_DST + 31;   // a byte no table uses (ndist <= 30): where a masked-off placement stores
 static_assert(hl::AREA == O_DST - O_LIT && hl::MAX_ENTRIES % PL == 0, "the run list lives in the literal/length symbol area");
@@ -170,34 +139,21 @@ __device__ __forceinline__ unsigned ring_at(uint32_t e)
     return k < 8 ? O_HIST + 8 * k : O_CLS + 8 * (k - 8);
 }
 
-// Per-lane LDS addressing.  Default: one lane's area is contiguous, lanes
-// STRIDE bytes apart (158 dwords, an even count: same-offset accesses of
-// lanes l and l + 16 share a bank, and table lookups at lane-dependent
-// offsets collide at random).  BPMD3_ILV=1 interleaves the 64 areas by
-// dword -- dword w of lane l at 256 w + 4 l of the workgroup's block -- so
-// every lane stays in bank l mod 32 whatever the offset (MI355X_MICROARCH.md
-// LDS: ds_read_b32 serves lanes 0-31 and 32-63 one cycle each): C2's
-// SQ_LDS_BANK_CONFLICT 36.5 M -> 0, but each table lookup's address costs two
-// more VALU instructions (SQ_INSTS_VALU 471 M -> 501 M) and the decoder is
-// issue-bound, not LDS-bound (SQ_WAIT_INST_LDS 1.4 M of 1 428 M wave
-// cycles): C2 189.4-190.3 (contiguous) vs 184.4-185.3 GiB/s (interleaved),
-// three interleaved runs on one box (profiles/r05b_ab_lds_interleave.log,
-// r05b_c2_sq_interleaved.txt).
-#ifndef BPMD3_ILV
-#define BPMD3_ILV 0
-#endif
+// Per-lane LDS addressing: one lane's area is contiguous, lanes STRIDE bytes
+// apart.  Interleaving the 64 areas by dword removed every bank conflict and
+// lost 3 % on C2, the decoder being issue-bound (profiles/r05b_ab_lds_interleave.log).
 __device__ __forceinline__ uint8_t* lane_area(uint8_t* smem, unsigned lane)
 {
-    return BPMD3_ILV ? smem + 4 * lane : smem + lane * STRIDE;
+    return smem + lane * STRIDE;
 }
 // byte b / dword w of the lane's area (T = lane_area())
 __device__ __forceinline__ uint8_t* lb(uint8_t* T, uint32_t b)
 {
-    return BPMD3_ILV ? T + (((b >> 2) << 8) | (b & 3u)) : T + b;
+    return T + b;
 }
 __device__ __forceinline__ uint32_t* lw(uint8_t* T, uint32_t w)
 {
-    return BPMD3_ILV ? (uint32_t*)(T + (w << 8)) : (uint32_t*)T + w;
+    return (uint32_t*)T + w;
 }
 __device__ __forceinline__ uint2 ring_ld(uint8_t* T, uint32_t e)
 {
@@ -277,7 +233,7 @@ __device__ __forceinline__ void expander(uint8_t* T, bool valid, uint32_t m, uin
                                          uint32_t raw)
 {
     const int32_t full_status = raw ? ST_OK : ST_NEED_BUFFERS;
-    bool stopped = false;   // BPMD3_XCHK: this message has its result; its tokens up to END are dropped
+    bool stopped = false;   // this message has its result; its tokens up to END are dropped
     uint8_t* o = out;
     uint32_t cap = 0, hist = 0;
     auto slot = [&](uint32_t mm) {
@@ -396,7 +352,7 @@ __device__ __forceinline__ void expander(uint8_t* T, bool valid, uint32_t m, uin
                                 worked = true;
                             }
                             stop = true;
-                        } else if (BPMD3_XCHK && stopped) {
+                        } else if (stopped) {
                             // a token the decoder sent before it saw the stop bit
                             ++tail;
                             ++k;
@@ -404,22 +360,19 @@ __device__ __forceinline__ void expander(uint8_t* T, bool valid, uint32_t m, uin
                         } else {
                             uint32_t nl = e.y & 7u, ml = (e.y >> 3) & 511u;
                             const uint32_t dist = (e.y >> 12) & 0xffffu;
-                            bool halt = false;
                             int32_t hst = full_status;
-                            if (BPMD3_XCHK) {
-                                // the literals, one output byte each (pos <= cap here)
-                                const uint32_t left = cap - pos;
-                                halt = nl > left;
-                                nl = halt ? left : nl;
-                                ml = halt ? 0u : ml;
-                            }
+                            // the literals, one output byte each (pos <= cap here)
+                            const uint32_t left = cap - pos;
+                            bool halt = nl > left;
+                            nl = halt ? left : nl;
+                            ml = halt ? 0u : ml;
                             if (nl) {
                                 l_dst[j] = pos;
                                 l_val[j] = e.x;
                                 l_n[j] = nl;
                                 pos += nl;
                             }
-                            if (BPMD3_XCHK && ml) {
+                            if (ml) {
                                 // the match, in the reference's order (inflate_stream.ipp:475-514):
                                 // raw mode's full output, the distance, the full output, the cut
                                 const bool c_full = pos >= cap, c_dist = dist > pos + hist;
@@ -437,7 +390,7 @@ __device__ __forceinline__ void expander(uint8_t* T, bool valid, uint32_t m, uin
                                 cpat_st = 0;
                                 pos += ml;
                             }
-                            if (BPMD3_XCHK && halt) {
+                            if (halt) {
                                 // the message's result; the pieces taken so far are still stored
                                 out_len[m] = pos;
                                 status[m] = hst;
@@ -499,7 +452,7 @@ __device__ __forceinline__ void expander(uint8_t* T, bool valid, uint32_t m, uin
                     }
                 }
             }
-            lds_store((uint8_t*)lw(T, W_TAIL), BPMD3_XCHK ? (tail & TAIL_MASK) | (stopped ? TAIL_STOP : 0u) : tail);
+            lds_store((uint8_t*)lw(T, W_TAIL), (tail & TAIL_MASK) | (stopped ? TAIL_STOP : 0u));
         }
         L3_LAP(2);
         if (!__ballot(worked)) {   // the decoder is behind: leave it the SIMD
@@ -819,12 +772,11 @@ template <bool SEG>
 __device__ __forceinline__ void decoder(uint8_t* T, bool valid, uint32_t m, const uint8_t* __restrict__ in,
                                         const uint64_t* __restrict__ in_off, const uint32_t* __restrict__ in_len,
                                         const uint32_t* __restrict__ out_cap, uint32_t raw,
-                                        const uint32_t* __restrict__ mask_key, const uint32_t* __restrict__ hist_len,
-                                        uint32_t hist_max, uint32_t n_msgs, const uint32_t* __restrict__ order,
-                                        uint32_t* __restrict__ qctr, uint32_t s0,
+                                        const uint32_t* __restrict__ mask_key, uint32_t n_msgs,
+                                        const uint32_t* __restrict__ order, uint32_t* __restrict__ qctr, uint32_t s0,
                                         const bp::SegTask* __restrict__ tasks)
 {
-    constexpr bool XC = !SEG && BPMD3_XCHK != 0;   // the expander makes the output checks
+    constexpr bool XC = !SEG;   // the byte path: the expander makes the output checks
     const uint32_t tail = raw ? 0u : 4u;
     const int32_t full_status = SEG ? bp::SEG_FULL : raw ? ST_OK : ST_NEED_BUFFERS;
     // segment mode: payload bit of the view's first bit, the view's bits, and
@@ -850,7 +802,7 @@ __device__ __forceinline__ void decoder(uint8_t* T, bool valid, uint32_t m, cons
     };
     // per-message state (set by begin())
     const uint8_t* A = in;
-    uint32_t s = 0, n = 0, cap = 0, mk = 0, hist = 0;
+    uint32_t s = 0, n = 0, cap = 0, mk = 0;
     // bit reader: bb holds up to 64 bits; refills take 32-bit words from q
     // (a 16-byte block, shifted down as it is used), then from nx (the next
     // block, already in registers).  Blocks move nx <- sg <- memory only in
@@ -910,13 +862,6 @@ __device__ __forceinline__ void decoder(uint8_t* T, bool valid, uint32_t m, cons
     bool last = false, fin = true;   // fin: END token written
     uint32_t pos = 0, head = 0;
     Canon<15> tl, td;
-    // the compact words of tl / td and whether they cover the whole code
-    uint32_t WL[CKL], WD[CKD];
-    bool wide = BPMD3_CKL == 0;
-#pragma unroll
-    for (int i = 0; i < CKL; ++i) WL[i] = 0;
-#pragma unroll
-    for (int i = 0; i < CKD; ++i) WD[i] = 0;
     Canon<7> tc;
     // header state
     uint32_t nlen = 0, ndist = 0, want = 0, have = 0, prev = 0;
@@ -989,9 +934,6 @@ __device__ __forceinline__ void decoder(uint8_t* T, bool valid, uint32_t m, cons
             // bytes 4k - s .. 4k - s + 3, masked with key bytes (j - s) % 4
             // (mask.ipp:38-59), so one rotation of the key unmasks every dword
             mk = mask_key ? __builtin_amdgcn_alignbit(mask_key[mm], mask_key[mm], 8u * ((0u - s_) & 3u)) : 0u;
-            // context takeover (bpmd_inflate_takeover_batch): the hist bytes before
-            // the slot are the window Beast's inflater keeps across messages
-            if (!XC) hist = hist_len ? (hist_len[mm] < hist_max ? hist_len[mm] : hist_max) : 0u;
             open_view(p, in_len[mm] - byte0);
         }
         drop(8 * s + bit0);
@@ -1009,10 +951,6 @@ __device__ __forceinline__ void decoder(uint8_t* T, bool valid, uint32_t m, cons
         pos = 0;
 #pragma unroll
         for (int i = 0; i < 15; ++i) { tl.Q[i] = 0; td.Q[i] = 0; }
-#pragma unroll
-        for (int i = 0; i < CKL; ++i) WL[i] = 0;
-#pragma unroll
-        for (int i = 0; i < CKD; ++i) WD[i] = 0;
         tl.root = 9;
         td.root = 5;
 #pragma unroll
@@ -1072,13 +1010,10 @@ __device__ __forceinline__ void decoder(uint8_t* T, bool valid, uint32_t m, cons
         uint32_t kp[KLIT + 1], kc[KLIT], kL[KLIT], kx[KLIT];
         bool kinv[KLIT];
         kp[0] = 0;
-        // (a wave-uniform choice: the full search only while some lane's
-        // tables have more distinct lengths than the compact words hold)
-        const bool any_wide = BPMD3_CKL == 0 || __ballot(wide) != 0;
 #pragma unroll
         for (int k = 0; k < KLIT; ++k) {
             kc[k] = rev15(w >> kp[k]);
-            const Sym y = any_wide ? canon_decode<15>(tl.Q, kc[k]) : canon_decode<CKL, 15>(WL, kc[k]);
+            const Sym y = canon_decode<15>(tl.Q, kc[k]);
             kL[k] = y.L;
             kx[k] = y.idx;
             kinv[k] = y.inval;
@@ -1144,7 +1079,7 @@ __device__ __forceinline__ void decoder(uint8_t* T, bool valid, uint32_t m, cons
         len += (uint32_t)(w2 >> L) & lowmask(xl);
         const uint32_t used = L + (is_len ? xl : 0u);
         const uint32_t d15 = rev15(w2 >> used);
-        const Sym yd = any_wide ? canon_decode<15>(td.Q, d15) : canon_decode<CKD, 15>(WD, d15);
+        const Sym yd = canon_decode<15>(td.Q, d15);
         const uint32_t Ld = yd.L;
         const uint32_t dsym = *lb(T, O_DST + yd.idx);
         const bool invd = yd.inval || dsym >= 30;
@@ -1179,18 +1114,16 @@ __device__ __forceinline__ void decoder(uint8_t* T, bool valid, uint32_t m, cons
             pos += tok ? (is_len ? len : 1u) : 0u;
             return;
         }
-        // output checks in the reference's order (inflate_stream.ipp:475-514)
-        const bool c_raw = !SEG && raw && pos >= cap;
-        const bool c_dist = !SEG && is_match && dist > pos + hist;
+        // segment mode: the slot's end is the only output check (a match may
+        // reach before the segment)
         const bool c_full = pos >= cap;
         uint32_t olen = is_match ? len : 1u;
         const bool c_trunc = pos + olen > cap;
         olen = c_trunc ? cap - pos : olen;
-        const bool emit = tok && !c_raw && !c_dist && !c_full;
-        const bool stop_full = tok && (c_raw || (!c_dist && (c_full || c_trunc)));
-        const bool stop_dist = tok && !c_raw && c_dist;
-        result = stop_full ? full_status : stop_dist ? ST_INVALID_DISTANCE : (mt && ev == 3) ? err : result;
-        st = (stop_full || stop_dist || (mt && ev >= 2)) ? (uint32_t)S_DONE : (mt && ev == 1) ? (uint32_t)S_TYPE : st;
+        const bool emit = tok && !c_full;
+        const bool stop_full = tok && (c_full || c_trunc);
+        result = stop_full ? full_status : (mt && ev == 3) ? err : result;
+        st = (stop_full || (mt && ev >= 2)) ? (uint32_t)S_DONE : (mt && ev == 1) ? (uint32_t)S_TYPE : st;
         emlen = emit && is_match ? olen : 0u;
         edist = emit && is_match ? dist : 0u;
         enl = emit && !is_match ? 1u : enl;
@@ -1324,12 +1257,6 @@ __device__ __forceinline__ void decoder(uint8_t* T, bool valid, uint32_t m, cons
                             tl.Q[i] = kFixL[i];
                             td.Q[i] = kFixD[i];
                         }
-                        // fixed: literal/length lengths 7, 8, 9; distances 5
-#pragma unroll
-                        for (int i = 0; i < CKL; ++i) WL[i] = i < 3 ? kFixL[6 + i] : 0u;
-#pragma unroll
-                        for (int i = 0; i < CKD; ++i) WD[i] = i < 1 ? kFixD[4] : 0u;
-                        wide = BPMD3_CKL == 0;
                         tl.root = 9;
                         td.root = 5;
                         st = S_DATA;
@@ -1579,7 +1506,7 @@ __device__ __forceinline__ void decoder(uint8_t* T, bool valid, uint32_t m, cons
                             if (a <= 256 && 256 < b) eob_seen = true;
                             // the run's list entry (no return value; past the
                             // area's capacity the header cannot fit anyway)
-                            if (BPMD3_PLIST && nent < hl::MAX_ENTRIES)
+                            if (nent < hl::MAX_ENTRIES)
                                 *(uint16_t*)lb(T, O_LIT + hl::entry_off(nent)) = (uint16_t)hl::entry_pack(a, val, rep);
                             ++nent;
                         }
@@ -1608,11 +1535,6 @@ __device__ __forceinline__ void decoder(uint8_t* T, bool valid, uint32_t m, cons
                     for (int l = 1; l < 16; ++l) c[l] = (h[l] >> 20) & 0x3ffu;
                     e = make_canon<15>(c, 6, 2, td);
                 }
-                if (!e && BPMD3_CKL) {
-                    const bool okl = compact_canon<15, CKL>(tl.Q, WL);
-                    const bool okd = compact_canon<15, CKD>(td.Q, WD);
-                    wide = !(okl && okd);
-                }
                 if (e) {
                     result = e;
                     st = S_DONE;
@@ -1636,7 +1558,7 @@ __device__ __forceinline__ void decoder(uint8_t* T, bool valid, uint32_t m, cons
                     have = 0;
                     // cl_: coded literal/length symbols.  The list path iff
                     // its entries and the placed symbols cannot collide
-                    const bool fits = BPMD3_PLIST && hl::list_fits(nent, cl_);
+                    const bool fits = hl::list_fits(nent, cl_);
                     st = fits ? S_PLIST : S_PASS2;
 #ifdef BPMD_PROF
                     l3fb_ += __builtin_popcountll(__ballot(!fits));
@@ -1649,22 +1571,17 @@ __device__ __forceinline__ void decoder(uint8_t* T, bool valid, uint32_t m, cons
         // list walk over the coded runs, or, for a header whose list does
         // not fit, the walk over every symbol's nibble.  Same placement
         // either way; a wave issues only the forms some lane of it needs.
-        if (BPMD3_PLIST && __ballot(st == S_PLIST)) {
+        if (__ballot(st == S_PLIST)) {
             if (st == S_PLIST) {
                 // the lane's next PL entries, read before anything is placed;
                 // entry have + j is the high (j even) or low half of ew[7 - j / 2]
                 uint32_t ew[PL / 2];
                 const uint32_t wb = (O_LIT + hl::AREA) / 4 - have / 2 - PL / 2;
-                if (BPMD3_ILV) {
 #pragma unroll
-                    for (uint32_t k = 0; k < PL / 2; ++k) ew[k] = *lw(T, wb + k);
-                } else {
-#pragma unroll
-                    for (uint32_t k = 0; k < PL / 4; ++k) {
-                        const uint2 v = *(const uint2*)(T + 4 * wb + 8 * k);
-                        ew[2 * k] = v.x;
-                        ew[2 * k + 1] = v.y;
-                    }
+                for (uint32_t k = 0; k < PL / 4; ++k) {
+                    const uint2 v = *(const uint2*)(T + 4 * wb + 8 * k);
+                    ew[2 * k] = v.x;
+                    ew[2 * k + 1] = v.y;
                 }
                 const uint32_t cnt = nent - have;
                 uint32_t en[PL], olds[PL], multi = 0;
@@ -1699,13 +1616,8 @@ __device__ __forceinline__ void decoder(uint8_t* T, bool valid, uint32_t m, cons
                 // from the list (placement never reaches it: the fit rule), so
                 // the turn indexes no register array.
                 if (__ballot(multi != 0)) {
-                    if (BPMD3_ILV) {
 #pragma unroll
-                        for (uint32_t j = 0; j < PL; ++j) *lw(T, W_NIB + j) = olds[j];
-                    } else {
-#pragma unroll
-                        for (uint32_t j = 0; j < PL; j += 2) *(uint2*)(T + O_NIB + 4 * j) = make_uint2(olds[j], olds[j + 1]);
-                    }
+                    for (uint32_t j = 0; j < PL; j += 2) *(uint2*)(T + O_NIB + 4 * j) = make_uint2(olds[j], olds[j + 1]);
                     while (__ballot(multi != 0)) {
                         if (multi) {
                             const uint32_t j = (uint32_t)__builtin_ctz(multi);
@@ -1803,9 +1715,11 @@ __device__ __forceinline__ void decoder(uint8_t* T, bool valid, uint32_t m, cons
         // publish and the wave's exit tests -- is then paid once per two
         // tokens (about half of the data lanes take it; a
         // third step, or refilling the input block first, measured neutral).
+        // (A one-trip loop left with break, not an if: as an if the compiler
+        // orders two independent instructions of each kernel the other way
+        // round, and this file's machine code is kept bit for bit.)
 #pragma unroll
-        for (int xs = 0; xs < BPMD3_XSTEPS; ++xs) {
-            if (BPMD3_XPIPE && nx_used && st0 == S_DATA && st == S_DATA) pipe();
+        for (int xs = 0; xs < 1; ++xs) {
             const bool room2 = (XC ? (head - taken) & TAIL_MASK : head - taken) < RING;
             if (!__ballot(st0 == S_DATA && st == S_DATA && !nx_used && room2)) break;
             uint32_t enl2 = 0, elit2 = 0, emlen2 = 0, edist2 = 0;
@@ -1869,8 +1783,7 @@ inflate_lane3_kernel(const uint8_t* __restrict__ in, const uint64_t* __restrict_
     __syncthreads();
     if (is_decoder) {
         if (BPMD3_DPRIO) __builtin_amdgcn_s_setprio(BPMD3_DPRIO);   // the decoder sets the pace
-        decoder<false>(T, valid, m, in, in_off, in_len, out_cap, raw, mask_key, hist_len, hist_max, n_msgs, order, qctr,
-                       s0, nullptr);
+        decoder<false>(T, valid, m, in, in_off, in_len, out_cap, raw, mask_key, n_msgs, order, qctr, s0, nullptr);
     } else {
         expander(T, valid, m, out, out_off, out_cap, out_len, status, hist_len, hist_max, qctr != nullptr, raw);
     }
@@ -1900,8 +1813,8 @@ inflate_lane3_seg_kernel(const uint8_t* __restrict__ in, const uint64_t* __restr
     __syncthreads();
     if (is_decoder) {
         if (BPMD3_DPRIO) __builtin_amdgcn_s_setprio(BPMD3_DPRIO);
-        decoder<true>(T, valid, valid ? j : 0u, in, in_off, in_len, nullptr, raw, nullptr, nullptr, 0u, n_tasks, nullptr,
-                      qctr, 0u, tasks);
+        decoder<true>(T, valid, valid ? j : 0u, in, in_off, in_len, nullptr, raw, nullptr, n_tasks, nullptr, qctr, 0u,
+                      tasks);
     } else {
         expander_seg(T, valid, valid ? j : 0u, sym, tasks, res, qctr != nullptr, in, in_off, in_len);
     }

@@ -99,9 +99,6 @@ __host__ __device__ constexpr uint32_t lag_compose(uint32_t first, uint32_t then
     for (uint32_t x = 0; x < 4; ++x) r |= ((then >> (2 * ((first >> (2 * x)) & 3u))) & 3u) << (2 * x);
     return r;
 }
-#ifndef BPMD_ZST_SCAN
-#define BPMD_ZST_SCAN 1   // 0: the scalar replay of round 5's first pfast
-#endif
 // a candidate token: A = c1 | x << 4 | c2 << 7 | dx << 11 | kind << 15 (bits of
 // the literal/length code incl. a sub-table's, length extra, distance code,
 // distance extra); B = (output bytes << 16) | literal or distance
@@ -146,9 +143,9 @@ enum : int { F_BLOCK = 1, F_FINISH = 5, F_TREES = 6 };   // zlib::Flush values t
 // 0 entry (state in), 1 block header, 2 table builds, 3 inflate_fast, 4 window
 // load, 5 match copies, 6 done() and state out, 7 whole call, 8 input
 // staging; counts: 9 copies, 10 fast-loop tokens, 11 output bytes, 12
-// stagings, 13 calls, 14 input bytes; inside inflate_fast: 15 bit refill +
-// literal/length lookup, 16 literal store, 17 length extra + distance decode,
-// 18 loop tail, 19 the cost of one lap (two clock reads); 24 symbols decoded
+// stagings, 13 calls, 14 input bytes; inside the wave-parallel inflate_fast:
+// 15 staging, 16 candidates, 17 chain, 18 output, 20 the whole of it, 21
+// windows, 22 tokens; 24 symbols decoded
 // by the slow path (LEN mode), 25 code-length symbols hdr_par committed, 26
 // block headers (TYPEDO)
 constexpr int ZPN = 32;
@@ -365,17 +362,12 @@ __device__ void zstream_run(Lds& L, State* __restrict__ st, const uint8_t* __res
         int32_t err = 0;
         const unsigned long long zf = ZP_NOW();
         (void)zf;
+        // (an unused clock read, left of the per-token lap counters: without it
+        // the prof build compiles to other instructions)
         unsigned long long zl = ZP_NOW();
         (void)zl;
         do {
             ZP_ADD(10, 1);
-#ifdef BPMD_ZSTREAM_LAPS
-            { const unsigned long long a = ZP_NOW(), b = ZP_NOW(); ZP_ADD(19, b - a); }
-#define ZLAP(i) do { const unsigned long long n_ = ZP_NOW(); ZP_ADD(i, n_ - zl); zl = n_; } while (0)
-#else
-#define ZLAP(i) ((void)0)
-#endif
-            ZLAP(18);
             if (bn < 15) {
                 pull();
                 pull();
@@ -387,10 +379,8 @@ __device__ void zstream_run(Lds& L, State* __restrict__ st, const uint8_t* __res
             }
             drop(slot_bits(s));
             const uint32_t kind = slot_kind(s), val = slot_val(s);
-            ZLAP(15);
             if (kind == K_VAL) {
                 put(val);
-                ZLAP(16);
             } else if (kind == K_LEN) {
                 uint32_t len = len_base(val);
                 const uint32_t x = len_extra(val);
@@ -421,7 +411,6 @@ __device__ void zstream_run(Lds& L, State* __restrict__ st, const uint8_t* __res
                 }
                 dist += bv & ((1u << dx) - 1u);
                 drop(dx);
-                ZLAP(17);
                 if (dist > op) {   // from the window
                     const uint64_t back = dist - op;
                     if (back > h.wsize) {
@@ -433,7 +422,6 @@ __device__ void zstream_run(Lds& L, State* __restrict__ st, const uint8_t* __res
                     len -= n;
                 }
                 if (len) copy_back(dist, len);   // from this call's output (room >= 258 here)
-                ZLAP(23);
             } else if (kind == K_EOB) {
                 h.mode = TYPE;
                 break;
@@ -549,7 +537,6 @@ __device__ void zstream_run(Lds& L, State* __restrict__ st, const uint8_t* __res
             const uint64_t op0 = op;
             uint32_t acc = 0, wout = 0;
             bool needwin = false;
-#if BPMD_ZST_SCAN
             // the chain of real token starts: one step per token on the scalar unit
             uint64_t mm[ZQ];
             {
@@ -674,79 +661,6 @@ __device__ void zstream_run(Lds& L, State* __restrict__ st, const uint8_t* __res
                 }
             }
             wout = wrel;
-#else
-            // the chain, replaying fast() (inflate_stream.ipp:979-1113)
-            uint32_t o = 0;
-#pragma unroll
-            for (uint32_t q = 0; q < ZQ; ++q) {
-                while (!stop && o < WAVE * (q + 1) && wout < ZWOUT) {
-                    const uint32_t a = rdlane(ca[q], o - WAVE * q);
-                    const uint32_t c1 = a & 15u, x = (a >> 4) & 7u, c2 = (a >> 7) & 15u, dx = (a >> 11) & 15u,
-                                   kind = (a >> 15) & 7u;
-                    if (bn < 15) {   // pull(); pull();
-                        ip += 2;
-                        bn += 16;
-                    }
-                    bn -= c1;
-                    if (kind == Z_EOB) {
-                        h.mode = TYPE;
-                        stop = true;
-                        break;
-                    }
-                    if (kind == Z_BADLIT) {
-                        err = ST_INVALID_LITERAL_LENGTH;
-                        stop = true;
-                        break;
-                    }
-                    const uint32_t b = rdlane(cb[q], o - WAVE * q);
-                    if (kind != Z_LIT) {
-                        if (x) {
-                            if (bn < x) {
-                                ip += 1;
-                                bn += 8;
-                            }
-                            bn -= x;
-                        }
-                        if (bn < 15) {
-                            ip += 2;
-                            bn += 16;
-                        }
-                        bn -= c2;
-                        if (kind == Z_BADDIST) {
-                            err = ST_INVALID_DISTANCE_CODE;
-                            stop = true;
-                            break;
-                        }
-                        if (bn < dx) {
-                            ip += 1;
-                            bn += 8;
-                            if (bn < dx) {
-                                ip += 1;
-                                bn += 8;
-                            }
-                        }
-                        bn -= dx;
-                        const uint64_t dist = b & 0xffffu, opc = op0 + wout;
-                        if (dist > opc) {   // from the window
-                            if (dist - opc > wsize) {
-                                err = ST_INVALID_DISTANCE;
-                                stop = true;
-                                break;
-                            }
-                            needwin = true;
-                        }
-                    }
-                    if (lane == 0) {
-                        L.ptok[acc] = b;
-                        atomicOr(&L.pbm[wout >> 5], 1u << (wout & 31));
-                    }
-                    ++acc;
-                    wout += b >> 16;
-                    o += c1 + x + c2 + dx;
-                    if (!(ip < in_last && op0 + wout < out_last)) stop = true;
-                }
-            }
-#endif
             ZP_ADD(21, 1);
             ZP_ADD(22, acc);
             ZP_ADD(17, ZP_NOW() - zq);

@@ -49,12 +49,6 @@ def main():
               f"({c[20] / max(1, c[22]):.0f} per token): staging {c[15] / k:.0f}, candidates {c[16] / k:.0f}, "
               f"chain {c[17] / k:.0f}, output {c[18] / k:.0f}")
         print(f"  outside inflate_fast and the header: {(c[7] - c[20] - c[3] - c[1] - c[0] - c[6]) / k:.0f} cycles per message")
-    if c[19]:   # the laps build (-DBPMD_ZSTREAM_LAPS): inside inflate_fast, per token
-        lap = c[19] / max(1, c[10])
-        print(f"  laps build, cycles per fast-loop token (one lap = {lap:.0f}, not subtracted):")
-        for i, nm in ((15, "refill + lookup"), (16, "literal store"), (17, "length + distance decode"),
-                      (23, "match copies"), (18, "loop tail")):
-            print(f"    {nm:26s} {c[i] / max(1, c[10]):8.0f}")
     if c[27] + c[28] + c[29] + c[30]:   # switch trips by mode (nested laps included)
         print(f"  by mode: type {c[27] / k:.0f}, stored {c[28] / k:.0f}, dynamic header {c[29] / k:.0f}, "
               f"LEN..LIT {c[30] / k:.0f}, other {c[31] / k:.0f} cycles per message; "
