@@ -30,7 +30,7 @@ constexpr int32_t SEG_DIRECT = 103;
 constexpr uint32_t KIND_START = 0;    // the payload's first bit
 constexpr uint32_t KIND_DYN = 1;      // a validated dynamic-block header (bit = its first bit)
 constexpr uint32_t KIND_STORED = 2;   // a validated stored block (bit = 8 x its LEN field's byte)
-constexpr uint32_t KIND_FIXED = 3;    // a fixed-code block reached by the skim (bit = its first bit)
+constexpr uint32_t KIND_FIXED = 3;    // a fixed-code block found by scan pass 2 (bit = its first bit)
 constexpr uint32_t KIND_NONE = 0xffu; // region without a candidate
 constexpr uint32_t KIND_PENDING = 0xfeu;  // scan pass 1: no stored block, the dynamic search pending
 
@@ -58,6 +58,11 @@ static_assert(sizeof(SegRes) == 16, "SegRes layout");
 // symbols of guard space before the first slot: a straddling 16-symbol load
 // of a match source starts at most 15 symbols before its slot
 constexpr uint32_t SYM_GUARD = 64;
+
+// what bp_stats_kernel sizes a payload's tasks and symbols by, and the
+// host's capacity arithmetic (bp_workspace.h) with it
+constexpr uint32_t R_MIN = 1024;   // smallest region, bytes
+constexpr uint32_t SLACK = 512;    // symbols of slack per slot
 
 }  // namespace bp
 }  // namespace bpmd

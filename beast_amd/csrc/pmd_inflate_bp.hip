@@ -16,7 +16,8 @@
 //      its region count and symbol workspace; exclusive sums give every
 //      payload's first task and workspace offset; bp_fit_kernel keeps the
 //      payloads that fit the stream's workspace capacity (the rest go to the
-//      wave kernel) -- no host read-back (see the driver below);
+//      wave kernel) -- no host read-back (see the driver below; the
+//      capacity's arithmetic is bp_workspace.h);
 //   2. scan (bp_scan_kernel, two passes, one wave per region): region 0's
 //      candidate is the payload's first bit; region k > 0 is searched for a
 //      stored block (LEN / NLEN, then a look at the block after it), and a
@@ -50,6 +51,7 @@
 #include <vector>
 
 #include "bp.h"
+#include "bp_workspace.h"
 #include "canon.h"
 #include "pmd_common.h"
 #include "pmd_internal.h"
@@ -57,11 +59,9 @@
 namespace bpmd {
 namespace bp {
 
-constexpr uint32_t SEG_OUT = 4096;       // target output per region (a C2 message's worth)
-constexpr uint32_t R_MIN = 1024, R_MAX = 8192;
+constexpr uint32_t R_MAX = 8192;         // region sizes: bp.h R_MIN .. R_MAX
 constexpr uint32_t STAGE_EXTRA = 320;    // staged bytes past a region: the longest dynamic header (2 283 bits)
 constexpr uint32_t STAGE_BYTES = R_MAX + STAGE_EXTRA + 16;   // + one dword before the region
-constexpr uint32_t SLACK = 512;          // symbols of slack per slot
 constexpr uint32_t SCAN_WAVES = 4;       // waves per scan workgroup (they share the Kraft table)
 
 // per-payload stats (index i of the long list)
@@ -83,12 +83,12 @@ bp_sum_kernel(const uint32_t* __restrict__ in_len, const uint32_t* __restrict__ 
     if ((threadIdx.x & 63) == 0 && acc) atomicAdd(total, acc);
 }
 
-// Region size: the batch's long bytes over 4 segments per lane of the chip
-// (BPMD_BP_SEGS; finer regions balance the segment kernel's lanes better,
-// at the cost of scanning more regions), within
-// [R_MIN, R_MAX].  Round 3 never went below SEG_OUT of output at the
-// payload's provisioned ratio (-DBPMD_BP_R_FLOOR), which left an 8-way shard
-// of C5 with 4 KiB regions and half the chip's lanes idle.
+// Region size: the batch's long bytes over segs_per_lane segments per lane
+// of the chip (SEGS_PER_LANE; finer regions balance the segment kernel's
+// lanes better, at the cost of scanning more regions), within
+// [R_MIN, R_MAX].  Round 3 never went below 4 KiB of output at the
+// payload's provisioned ratio, which left an 8-way shard of C5 with 4 KiB
+// regions and half the chip's lanes idle.
 __global__ void __launch_bounds__(256)
 bp_stats_kernel(const uint32_t* __restrict__ in_len, const uint32_t* __restrict__ out_cap,
                 const uint32_t* __restrict__ order, const uint32_t* __restrict__ nlong, uint32_t n,
@@ -105,18 +105,11 @@ bp_stats_kernel(const uint32_t* __restrict__ in_len, const uint32_t* __restrict_
         const uint32_t len = in_len[m], cap = out_cap[m];
         // output per compressed byte the caller provisioned, capped at 4
         const uint64_t e16 = cap >= 4ull * len ? (4ull << 16) : (((uint64_t)cap << 16) / (len ? len : 1u));
-        uint64_t R = cap ? ((uint64_t)SEG_OUT * len) / cap : R_MAX;
-        const uint64_t share = *total / ((uint64_t)segs_per_lane * (lanes ? lanes : 1u));
-#ifdef BPMD_BP_R_FLOOR   // diagnostics: round 3's rule (never below SEG_OUT of output)
-        R = R < share ? share : R;
-#else
         // the share alone: a batch with fewer long bytes than the chip's lanes
         // want cuts its payloads finer, down to R_MIN (about one of Beast's
         // 1023-symbol blocks of near-random data; an 8-way shard of C5 has
-        // 1 KiB a lane), not at SEG_OUT of output
-        (void)R;
-        R = share;
-#endif
+        // 1 KiB a lane), not at 4 KiB of output
+        uint64_t R = *total / ((uint64_t)segs_per_lane * (lanes ? lanes : 1u));
         R = R < R_MIN ? R_MIN : R > R_MAX ? R_MAX : R;
         R &= ~255ull;
         na = (uint32_t)((len + R / 2) / R);   // a last region shorter than R / 2 joins the one before
@@ -356,15 +349,11 @@ __device__ bool dyn_header_ok(const Bits& B, uint32_t b, uint32_t lim)
 // sized short, and 21-37 % of the payloads fell back to the wave kernel,
 // profiles/r06l_beast_shard.log).  A block it rejects -- a fixed block of
 // text with many matches, say -- is only not a segment start.  (FW * 9 bits
-// fit in STAGE_EXTRA.)
-#ifndef BPMD_BP_FIXED
-// bit 0: a stored block followed by a fixed block that passes fixed_block_ok
-// is a candidate (round 5: only an empty one); bit 1: pass 2 also searches
-// fixed-block starts after a fixed block's end-of-block code, checked by
-// fixed_block_ok and fixed_eob_at (without the latter, 21-37 % of C5's
-// Beast payloads fell back: profiles/r06l_beast_shard.log)
-#define BPMD_BP_FIXED 3
-#endif
+// fit in STAGE_EXTRA.)  Two places use it: a stored block followed by a
+// fixed block that passes is a candidate (round 5: only an empty one), and
+// pass 2 also searches fixed-block starts after a fixed block's end-of-block
+// code, checked by this and fixed_eob_at (without the latter, 21-37 % of
+// C5's Beast payloads fell back: profiles/r06l_beast_shard.log).
 constexpr uint32_t FW = 96, FMAX = 6;
 template <class Bits>
 __device__ bool fixed_block_ok(const Bits& B, uint32_t b, uint32_t lim)
@@ -500,7 +489,6 @@ __device__ bool stored_ok(const GlobalBits& G, const LdsBits& Lb, uint32_t bias,
     // peer's near-random payloads are runs of stored and fixed blocks
     if (type != 1) return false;
     if (L == 0) return true;
-    if (!(BPMD_BP_FIXED & 1)) return false;
     return staged && lq + 3 + FW * 9 + 32 <= lim ? fixed_block_ok(Lb, lq, lim) : fixed_block_ok(G, 8 * (s + q), 8 * (s + len));
 }
 
@@ -508,9 +496,6 @@ __device__ bool stored_ok(const GlobalBits& G, const LdsBits& Lb, uint32_t bias,
 // block, or the payload's start) to the next: a 4 KiB chunk's block (stored
 // at worst: 4 096 + 5) plus the next marker
 constexpr uint32_t MARK_SPAN = 4096 + 5 + 5 + 16;
-#ifndef BPMD_BP_MARK_END
-#define BPMD_BP_MARK_END 1   // 0: any marker marks the payload (round 5 until the ADVICE fix)
-#endif
 constexpr uint32_t LIST = 128;         // candidate offsets per wave and chunk
 constexpr uint32_t CHUNK_STEPS = 4;    // 4 x 2048 bit offsets between deep-check rounds
 constexpr uint32_t STORED_FLAG = 0x80000000u;
@@ -571,7 +556,7 @@ bp_scan_kernel(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_o
     if (DYN) {
         // only the regions pass 1 left pending, of unmarked payloads, and of
         // those every dyn_stride-th (a dynamic-header search costs a region's
-        // whole bit-offset scan; BPMD_BP_SEGS sweep of Beast's payloads,
+        // whole bit-offset scan; sweep of Beast's payloads,
         // profiles/r05h_bp_segs_sweep.log)
         const uint32_t gl = g0 + lane;
         bool need = false;
@@ -581,7 +566,7 @@ bp_scan_kernel(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_o
             // MARK_SPAN + R of the payload's end -- a foreign encoder's payload
             // that flushed once near its start is searched; bit 2
             // a stored block with data, which turns on the fixed-block search)
-            // The stride (BPMD_BP_DYN_STRIDE, else per payload): a payload with
+            // The stride (dyn_stride > 1, else per payload): a payload with
             // stored data blocks (near-random data: a Beast peer's stored and
             // fixed runs, bit 2) is searched in one region per 4 KiB whatever
             // the region size, so a small batch's fine regions (R down to
@@ -600,8 +585,7 @@ bp_scan_kernel(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_o
             // (a region the stride passes over still gets the fixed-block
             // search when the payload has it: that one is cheap)
             const bool fixed_only = kr % ds != 0 && kr + 1 != sr.regions;
-            if (((mk & 3u) | (BPMD_BP_MARK_END ? 0u : 2u)) == 3u ||
-                (fixed_only && !((BPMD_BP_FIXED & 2) && (mk & 4u)))) {
+            if ((mk & 3u) == 3u || (fixed_only && !(mk & 4u))) {
                 tasks[gl].kind = KIND_NONE;
             } else {
                 // a region inside the data of a stored block pass 1 found (one
@@ -610,7 +594,7 @@ bp_scan_kernel(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_o
                 // marker; Beast's binary payloads are 35-60 % stored blocks)
                 const uint32_t k = gl - task_base[ri], R = stats[ri].R;
                 // the region's real end: the last region also takes the
-                // payload's remainder (region_of), which may hold a block
+                // payload's remainder (bp_stats_kernel), which may hold a block
                 // start past the stored block's data
                 const uint32_t rend = k + 1 == stats[ri].regions ? in_len[order[ri]] : (k + 1) * R;
                 bool inside = false;
@@ -639,7 +623,7 @@ bp_scan_kernel(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_o
         const uint32_t i = (uint32_t)__builtin_amdgcn_readfirstlane((int)region_map[g]);
         const uint32_t m = order[i];
         const Stat st = stats[i];
-        const bool fixed_on = (BPMD_BP_FIXED & 2) && DYN && (marked[i] & 4u);   // pass 1's marks (an earlier launch)
+        const bool fixed_on = DYN && (marked[i] & 4u);   // pass 1's marks (an earlier launch)
         // the dynamic-header search only in every ds-th region of a payload
         // with stored data blocks (and its last); the others search fixed
         // starts only (the screening above)
@@ -671,7 +655,7 @@ bp_scan_kernel(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_o
                 const uint32_t nwords = STAGE_BYTES / 4 + 8;
                 const uint32_t tailm = ((s + len) & 3u) ? (1u << (8 * ((s + len) & 3u))) - 1u : ~0u;
                 // only the words this region's size needs are loaded (the last
-                // region also holds the payload's remainder, region_of: up to
+                // region also holds the payload's remainder, bp_stats_kernel: up to
                 // 1.5 R, searched as far as the stage holds it)
                 const uint32_t rlen = (k + 1 == st.regions ? len : (k + 1) * st.R) - k * st.R;
                 const uint32_t nw = (rlen + STAGE_EXTRA + 64) / 4 < nwords ? (rlen + STAGE_EXTRA + 64) / 4 : nwords;
@@ -891,221 +875,6 @@ bp_scan_kernel(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_o
     }
 }
 
-// ------------------------------------------------------------------- skim
-// A Beast peer's long payloads carry no sync markers: tr_flush_block cuts a
-// block every lit_bufsize - 1 symbols and picks stored, fixed or dynamic by
-// size (deflate_stream.ipp:1406, :1425-1518), and near-random data gives
-// runs of stored and FIXED blocks.  A fixed block's header is three bits
-// that any bit offset can look like, so no scan finds it, and a run of them
-// was one serial segment.  The skim starts one lane at every candidate pass
-// 1 found (a stored block, or the payload's first bit) and walks the blocks
-// after it: a stored block by its LEN field, a fixed block symbol by symbol
-// with the fixed code (inflate_stream.ipp:865-930; no tables, no output),
-// until a dynamic block, the next candidate, a final block or an error.
-// Every block start it passes becomes its region's candidate when the region
-// has none (a dynamic block's start too), and the regions it crossed without
-// a block start are settled as candidate-free, so pass 2 searches only the
-// regions no walk reached.  A walk that meets anything unexpected simply
-// stops: candidates only ever cut the serial decode, which checks
-// everything again (bit-exact results do not depend on the skim).
-struct SkimBits {
-    const uint32_t* A;   // the payload's aligned base
-    uint32_t E;          // dwords holding payload bytes
-    uint32_t sbits;      // 8 x the payload's offset in A[0]
-    __device__ __forceinline__ uint32_t word(uint32_t w) const { return w < E ? A[w] : 0u; }
-};
-
-// the region of payload byte `byte` (bp_stats_kernel: na regions of R bytes,
-// the last one taking the rest)
-__device__ __forceinline__ uint32_t region_of(uint32_t byte, uint32_t R, uint32_t na)
-{
-    const uint32_t k = byte / R;
-    return k < na ? k : na - 1;
-}
-
-__global__ void __launch_bounds__(256)
-bp_skim_kernel(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_off,
-               const uint32_t* __restrict__ in_len, const uint32_t* __restrict__ order,
-               const uint32_t* __restrict__ region_map, const uint32_t* __restrict__ n_regions_dev,
-               const Stat* __restrict__ stats, const uint32_t* __restrict__ task_base, SegTask* __restrict__ tasks,
-               const uint32_t* __restrict__ marked)
-{
-    const uint32_t n_regions = *n_regions_dev;
-    for (uint32_t g = blockIdx.x * 256u + threadIdx.x; g < n_regions; g += gridDim.x * 256u) {
-    const SegTask t0 = tasks[g];
-    if (t0.kind != KIND_START && t0.kind != KIND_STORED) continue;
-    const uint32_t i = region_map[g];
-    if ((marked[i] & 3u) == 3u) continue;   // sync markers: pass 1 found the chunk starts
-    const Stat st = stats[i];
-    const uint32_t tb = task_base[i];
-    const uint32_t k0 = g - tb;
-    const uint32_t m = order[i];
-    const uint32_t len = in_len[m];
-    const uint8_t* p = in + in_off[m];
-    const uint32_t s = (uint32_t)((uintptr_t)p & 3u);
-    SkimBits B{(const uint32_t*)(p - s), (s + len + 3) >> 2, 8 * s};
-    // the next candidate pass 1 found (stored: its LEN field's bit)
-    uint32_t next_bit = 8 * len;
-    for (uint32_t k = k0 + 1; k < st.regions; ++k) {
-        const uint32_t kd = tasks[tb + k].kind;
-        if (kd == KIND_STORED) {
-            next_bit = tasks[tb + k].bit;
-            break;
-        }
-    }
-    const uint32_t end_bits = 8 * len;
-    // bit reader: 64 bits at `pos` from the dwords at w0 (+ the next one)
-    uint32_t pos;
-    bool stored_now;
-    if (t0.kind == KIND_STORED) {
-        pos = t0.bit;   // the LEN field
-        stored_now = true;
-    } else {
-        pos = 0;
-        stored_now = false;
-    }
-    uint32_t last_k = k0;   // the region of the last block start recorded (or the walk's own)
-    auto settle = [&](uint32_t kto) {   // regions after last_k up to kto (exclusive): no block start
-        for (uint32_t k = last_k + 1; k < kto && k < st.regions; ++k)
-            if (tasks[tb + k].kind == KIND_PENDING) tasks[tb + k].kind = KIND_NONE;
-    };
-    auto record = [&](uint32_t bit, uint32_t kind) {
-        const uint32_t k = region_of(bit >> 3, st.R, st.regions);
-        if (k <= last_k) return;   // a region that has its start already
-        settle(k);
-        SegTask& t = tasks[tb + k];
-        if (t.kind == KIND_PENDING || t.kind == KIND_NONE) {
-            t.bit = bit;
-            t.kind = kind;
-        }
-        last_k = k;
-    };
-    // bit reader: bb holds nb bits; refills take dwords from the 16-byte
-    // block q; the next three blocks are already loading (a fixed block of
-    // near-random bytes uses a block every ~14 symbols, and one block ahead
-    // left the walk waiting on memory at every block)
-    uint4 q = make_uint4(0, 0, 0, 0), n1 = q, n2 = q, n3 = q;
-    uint32_t qi = 0, bi = 0;   // dword index in q; block index of n3
-    uint64_t bb = 0;
-    uint32_t nb = 0;
-    auto load_block = [&](uint32_t b) -> uint4 {   // 16-byte block b of A, zeros past the payload
-        return 16 * b < 4 * B.E ? *(const uint4*)(B.A + 4 * b) : make_uint4(0, 0, 0, 0);
-    };
-    auto reset = [&](uint32_t at) {   // position the reader at payload bit `at`
-        const uint32_t qb = B.sbits + at;
-        const uint32_t blk = qb >> 7;
-        q = load_block(blk);
-        n1 = load_block(blk + 1);
-        n2 = load_block(blk + 2);
-        n3 = load_block(blk + 3);
-        bi = blk + 3;
-        qi = (qb >> 5) & 3u;
-        const uint32_t d = qi == 0 ? q.x : qi == 1 ? q.y : qi == 2 ? q.z : q.w;
-        bb = (uint64_t)(d >> (qb & 31u));
-        nb = 32 - (qb & 31u);
-        ++qi;
-        pos = at;
-    };
-    auto fill = [&]() {
-        if (nb <= 32) {
-            if (qi == 4) {
-                q = n1;
-                n1 = n2;
-                n2 = n3;
-                n3 = load_block(++bi);
-                qi = 0;
-            }
-            const uint32_t d = qi == 0 ? q.x : qi == 1 ? q.y : qi == 2 ? q.z : q.w;
-            bb |= (uint64_t)d << nb;
-            nb += 32;
-            ++qi;
-        }
-    };
-    auto take = [&](uint32_t n) {   // n <= 32 bits, after fill()
-        const uint32_t v = (uint32_t)bb & (n >= 32 ? ~0u : ((1u << n) - 1u));
-        bb >>= n;
-        nb -= n;
-        pos += n;
-        return v;
-    };
-    reset(pos);
-    for (uint32_t guard = 0; guard < 4096; ++guard) {
-        if (stored_now) {
-            // LEN NLEN at `pos` (byte aligned), then the bytes
-            if (pos + 32 > end_bits) break;
-            fill();
-            const uint32_t v = take(32);
-            const uint32_t L = v & 0xffffu;
-            if (L != ((v >> 16) ^ 0xffffu)) break;
-            const uint32_t nxt = pos + 8 * L;
-            if (nxt >= end_bits) break;
-            reset(nxt);
-            stored_now = false;
-        }
-        // a block header at pos
-        if (pos >= next_bit || pos + 3 > end_bits) break;
-        fill();
-        const uint32_t h = take(3);
-        if (h & 1) break;   // a final block: nothing after it
-        const uint32_t type = h >> 1;
-        if (type == 0) {
-            const uint32_t lb = (pos + 7) & ~7u;   // the LEN field
-            if (lb >= next_bit) break;             // the next candidate's block: its walk
-            record(lb, KIND_STORED);
-            reset(lb);
-            stored_now = true;
-            continue;
-        }
-        if (type != 1) {   // dynamic (or invalid): a candidate, and the walk ends
-            if (type == 2) record(pos - 3, KIND_DYN);
-            break;
-        }
-        record(pos - 3, KIND_FIXED);
-        // the fixed block's symbols up to its end-of-block
-        bool ok = false;
-        for (uint32_t n = 0; n < 65536; ++n) {
-            fill();
-            if (pos + 7 > end_bits) break;
-            const uint32_t c9 = __builtin_bitreverse32((uint32_t)bb) >> 23;   // the next 9 code bits, first bit high
-            uint32_t L, sym;
-            if ((c9 >> 2) < 24) {
-                L = 7;
-                sym = 256 + (c9 >> 2);
-            } else if ((c9 >> 1) < 192) {
-                L = 8;
-                sym = (c9 >> 1) - 48;
-            } else if ((c9 >> 1) < 200) {
-                L = 8;
-                sym = 280 + (c9 >> 1) - 192;
-            } else {
-                L = 9;
-                sym = 144 + c9 - 400;
-            }
-            take(L);
-            if (sym == 256) {
-                ok = true;
-                break;
-            }
-            if (sym < 256) continue;
-            if (sym > 285) break;   // invalid literal/length code
-            const uint32_t li = sym - 257;
-            const uint32_t xl = (li < 8 || li == 28) ? 0u : ((li - 4) >> 2);
-            fill();
-            take(xl);
-            const uint32_t dsym = __builtin_bitreverse32((uint32_t)bb) >> 27;
-            take(5);
-            if (dsym >= 30) break;   // invalid distance code
-            const uint32_t xd = dsym < 4 ? 0u : (dsym >> 1) - 1;
-            fill();
-            take(xd);
-        }
-        if (!ok || pos > end_bits) break;
-    }
-    // the regions the walk crossed up to where it stopped hold no other start
-    settle(region_of((pos < end_bits ? pos : end_bits - 1) >> 3, st.R, st.regions));
-    }
-}
-
 // Slots, one wave per long payload once every region is scanned: each
 // candidate's span runs to the next candidate (or the end of the payload);
 // slot = span x F16 + SLACK symbols, laid out in order.
@@ -1199,10 +968,7 @@ typedef uint2 uint2_sa __attribute__((aligned(2)));
 // same as 16 on 8-way C4 / C5 shards (8.63 vs 8.65 ms, 2.41 vs 2.40 ms); a
 // build with 64 did not finish its first C4 shard call within 180 s and was
 // not pursued (profiles/r05n_resolve_width.log)
-#ifndef BPMD_BP_RSYM
-#define BPMD_BP_RSYM 16
-#endif
-constexpr uint32_t RSYM = BPMD_BP_RSYM;
+constexpr uint32_t RSYM = 16;
 
 __global__ void __launch_bounds__(256)
 bp_resolve_kernel(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_off,
@@ -1371,264 +1137,14 @@ bp_resolve_kernel(const uint8_t* __restrict__ in, const uint64_t* __restrict__ i
     }
 }
 
-// ------------------------------------------------- segment-parallel resolve
-// Round 4's resolve walked each payload's segments in order on one wave,
-// because a reference reads bytes the earlier segments write: a 64 KiB
-// payload was 64 dependent steps, and the longest payloads set the kernel's
-// end.  Now two kernels, the phase boundary between them a kernel boundary
-// (no workgroup ever waits for another):
-//   bp_chain_kernel   one lane per payload walks the chain of segment
-//                     results only (no symbols): each on-chain segment's
-//                     output start and slot, the capacity cut, the status,
-//                     the fallbacks;
-//   bp_resolve2_kernel one workgroup per payload (a queue over payloads)
-//                     resolves all its segments at once: a reference is
-//                     followed into the SYMBOLS of the segment that holds its
-//                     target (found by a binary search over the chain's
-//                     output starts in LDS) and on, while the target is itself
-//                     a reference -- symbols never change after decoding, so
-//                     no order between segments is needed.  The first
-//                     reference before the payload's start (the reference's
-//                     invalid_distance, inflate_stream.ipp:475-514) is found
-//                     in a first pass, so no byte at or past it is written.
-struct PayRes {
-    uint32_t nseg;     // segments on the chain up to the terminating one
-    uint32_t olen;     // output length by the chain alone (capacity / status)
-    int32_t status;    // status by the chain alone
-    uint32_t flags;    // 1 fallback (wave kernel), 2 capacity cut
-};
-static_assert(sizeof(PayRes) == 16, "PayRes layout");
-
-__global__ void __launch_bounds__(256)
-bp_chain_kernel(const uint32_t* __restrict__ order, const uint32_t* __restrict__ nlong,
-                const uint32_t* __restrict__ task_base, const SegTask* __restrict__ tasks,
-                const SegRes* __restrict__ res, const uint32_t* __restrict__ out_cap, uint32_t raw,
-                const Stat* __restrict__ stats, uint32_t* __restrict__ chp, uint64_t* __restrict__ chs,
-                PayRes* __restrict__ pay, uint32_t* __restrict__ out_len, int32_t* __restrict__ status,
-                uint32_t* __restrict__ fb_list, uint32_t* __restrict__ fb_count)
-{
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= *nlong) return;
-    const uint32_t m = order[i];
-    const uint32_t cap = out_cap[m];
-    const uint32_t tb = task_base[i];
-    const int32_t full_status = raw ? ST_OK : ST_NEED_BUFFERS;
-    PayRes pr = {0, 0, ST_OK, 0};
-    if (stats[i].regions == 0) {
-        pr.flags = 1;
-    } else {
-        uint32_t t = tb, P = 0, k = 0;
-        for (;;) {
-            const SegRes r = res[t];
-            if (r.status == SEG_DIRECT) {   // (no symbols: this form sends the payload to the wave kernel)
-                pr.flags = 1;
-                break;
-            }
-            chp[tb + k] = P;
-            chs[tb + k] = tasks[t].sym_off;
-            ++k;
-            if (r.nsym > cap - P) {   // the capacity cuts this segment
-                pr.status = full_status;
-                pr.olen = cap;
-                pr.flags = 2;
-                break;
-            }
-            P += r.nsym;
-            if (r.status == SEG_HANDOFF && r.next > t && r.next != 0xffffffffu) {
-                t = r.next;
-                continue;
-            }
-            if (r.status == SEG_FULL || r.status == SEG_SKIP || r.status == SEG_HANDOFF) {
-                pr.flags = 1;
-                {
-                    g_bp_fb[0] = m;
-                    g_bp_fb[1] = t - tb;
-                    g_bp_fb[2] = (uint32_t)r.status;
-                    g_bp_fb[3] = r.nsym;
-                    g_bp_fb[4] = tasks[t].sym_cap;
-                    g_bp_fb[5] = r.next;
-                    g_bp_fb[6] = tasks[t].bit;
-                    g_bp_fb[7] = tasks[t].kind;
-                }
-                break;
-            }
-            pr.status = r.status;
-            pr.olen = P;
-            break;
-        }
-        pr.nseg = k;
-        atomicAdd(&g_bp_diag[1], (unsigned long long)k);
-    }
-    atomicAdd(&g_bp_diag[0], 1ull);
-    if (pr.flags & 1) {
-        atomicAdd(&g_bp_diag[2], 1ull);
-        fb_list[atomicAdd(fb_count, 1u)] = m;
-    }
-    pay[i] = pr;
-    (void)out_len;
-    (void)status;
-}
-
-constexpr uint32_t RES_THREADS = 256;
-constexpr uint32_t RES_LDS_SEGS = 1024;   // chains up to this length resolve from LDS
-constexpr uint32_t RES_HOPS = 32;         // references followed per byte in pass 2
-
-// the chain segment holding output position q (chp ascending, chp[0] = 0)
-__device__ __forceinline__ uint32_t seg_of(const uint32_t* __restrict__ P, uint32_t K, uint32_t q)
-{
-    uint32_t lo = 0, hi = K - 1;   // largest k with P[k] <= q
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi + 1) >> 1;
-        if (P[mid] <= q) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
-}
-
-__global__ void __launch_bounds__(RES_THREADS)
-bp_resolve2_kernel(const uint32_t* __restrict__ order, const uint32_t* __restrict__ nlong,
-                   const uint32_t* __restrict__ task_base, const uint16_t* __restrict__ sym,
-                   uint8_t* __restrict__ out, const uint64_t* __restrict__ out_off,
-                   const uint32_t* __restrict__ out_cap, uint32_t* __restrict__ out_len,
-                   int32_t* __restrict__ status, uint32_t raw, const uint32_t* __restrict__ chp,
-                   const uint64_t* __restrict__ chs, const PayRes* __restrict__ pay, uint32_t* __restrict__ qctr)
-{
-    __shared__ uint32_t sP[RES_LDS_SEGS];
-    __shared__ uint64_t sS[RES_LDS_SEGS];
-    __shared__ uint32_t s_i, s_bad, s_deep;
-    const uint32_t tid = threadIdx.x;
-    const uint32_t end = *nlong;
-    for (;;) {
-        if (tid == 0) s_i = atomicAdd(qctr, 1u);
-        __syncthreads();
-        const uint32_t i = s_i;
-        if (i >= end) break;
-        const PayRes pr = pay[i];
-        if (pr.flags & 1) {   // the wave kernel decodes it (bp_chain_kernel listed it)
-            __syncthreads();
-            continue;
-        }
-        const uint32_t m = order[i];
-        const uint32_t cap = out_cap[m];
-        uint8_t* o = out + out_off[m];
-        const uint32_t tb = task_base[i];
-        const uint32_t K = pr.nseg;
-        const bool lds = K <= RES_LDS_SEGS;
-        for (uint32_t k = tid; k < K && lds; k += RES_THREADS) {
-            sP[k] = chp[tb + k];
-            sS[k] = chs[tb + k];
-        }
-        if (tid == 0) {
-            s_bad = 0xffffffffu;
-            s_deep = 0;
-        }
-        __syncthreads();
-        const uint32_t* P = lds ? sP : chp + tb;
-        const uint64_t* S = lds ? sS : chs + tb;
-        // positions whose references count: the output, plus (pmd mode) the
-        // token at the capacity when the capacity cut the chain -- a bad
-        // distance there is the reference's error, not need_buffers
-        const uint32_t lim = pr.olen + ((pr.flags & 2) && !raw ? 1u : 0u);
-        // pass 1: the first reference before the payload's start
-        for (uint32_t k = 0; k < K; ++k) {
-            const uint32_t p0 = P[k], p1 = k + 1 < K ? P[k + 1] : lim;
-            const uint32_t n = p1 > p0 ? p1 - p0 : 0u;
-            const uint16_t* sy = sym + S[k];
-            for (uint32_t j = tid * 4; j < n; j += RES_THREADS * 4) {
-#pragma unroll
-                for (uint32_t q = 0; q < 4; ++q) {
-                    if (j + q < n) {
-                        const uint32_t v = sy[j + q];
-                        if ((v & SYM_REF) && (v & 0x7fffu) + 1 > p0) atomicMin(&s_bad, p0 + j + q);
-                    }
-                }
-            }
-        }
-        __syncthreads();
-        const uint32_t bad = s_bad;
-        const uint32_t olen = bad < lim ? bad : pr.olen;
-        // pass 2: bytes [0, olen), 4 per thread per step; a reference is
-        // followed through the symbols until a literal, at most RES_HOPS
-        // times (a run of one byte repeated across many segments -- a
-        // distance-1 match carried from segment to segment -- would take one
-        // hop per segment for every byte: such a payload is finished by
-        // pass 3 instead)
-        bool deep = false;
-        for (uint32_t k = 0; k < K; ++k) {
-            const uint32_t p0 = P[k];
-            if (p0 >= olen) break;
-            const uint32_t p1 = k + 1 < K ? (P[k + 1] < olen ? P[k + 1] : olen) : olen;
-            const uint16_t* sy = sym + S[k];
-            for (uint32_t j = tid * 4; p0 + j < p1; j += RES_THREADS * 4) {
-                uint32_t b[4];
-#pragma unroll
-                for (uint32_t q = 0; q < 4; ++q) {
-                    b[q] = 0;
-                    if (p0 + j + q < p1) {
-                        uint32_t v = sy[j + q];
-                        uint32_t base = p0;   // output start of the segment v belongs to
-                        for (uint32_t h = 0; (v & SYM_REF) && h < RES_HOPS; ++h) {
-                            const uint32_t t = base - ((v & 0x7fffu) + 1);   // >= 0 before `bad`
-                            const uint32_t kk = seg_of(P, K, t);
-                            base = P[kk];
-                            v = sym[S[kk] + (t - base)];
-                        }
-                        deep = deep || (v & SYM_REF);
-                        b[q] = v & 0xffu;
-                    }
-                }
-                const uint32_t x = p0 + j;
-                if (x + 4 <= p1) {
-                    *(uint32_ua*)(o + x) = b[0] | (b[1] << 8) | (b[2] << 16) | (b[3] << 24);
-                } else {
-#pragma unroll
-                    for (uint32_t q = 0; q < 4; ++q)
-                        if (x + q < p1) o[x + q] = (uint8_t)b[q];
-                }
-            }
-        }
-        if (deep) s_deep = 1;
-        __syncthreads();
-        if (s_deep) {
-            // pass 3: segment by segment in stream order, a reference reading
-            // the byte the earlier segments wrote (round 4's resolve, with the
-            // workgroup's four waves on each segment; the barrier makes the
-            // bytes visible across them)
-            for (uint32_t k = 0; k < K; ++k) {
-                const uint32_t p0 = P[k];
-                if (p0 >= olen) break;
-                const uint32_t p1 = k + 1 < K ? (P[k + 1] < olen ? P[k + 1] : olen) : olen;
-                const uint16_t* sy = sym + S[k];
-                for (uint32_t j = tid * 4; p0 + j < p1; j += RES_THREADS * 4) {
-#pragma unroll
-                    for (uint32_t q = 0; q < 4; ++q) {
-                        if (p0 + j + q < p1) {
-                            const uint32_t v = sy[j + q];
-                            o[p0 + j + q] = (v & SYM_REF) ? o[p0 - ((v & 0x7fffu) + 1)] : (uint8_t)v;
-                        }
-                    }
-                }
-                __syncthreads();
-            }
-        }
-        if (tid == 0) {
-            const bool inval = bad < lim;
-            out_len[m] = olen;
-            // (bad < lim: before the capacity in raw mode, at or before it in
-            // pmd mode -- the serial decoder's order of the two checks)
-            status[m] = inval ? ST_INVALID_DISTANCE : pr.status;
-        }
-        __syncthreads();
-    }
-}
-
 }  // namespace bp
 }  // namespace bpmd
 
 // ------------------------------------------------------------------ driver
 // Long payloads order[0, *nlong) of a batch (pmd_capi.hip inflate_impl); the
 // rest of the batch is the caller's.  n: the batch's message count (bounds
-// nlong).  The decode workspace has a per-(device, stream) capacity:
+// nlong).  The decode workspace has a per-(device, stream) capacity, whose
+// arithmetic is bp_workspace.h:
 //   * the first call on a stream sizes it to that call's needs (one read-back
 //     of the totals, the only wait of the path), or bpmd_inflate_reserve()
 //     sets it beforehand with no wait at all;
@@ -1640,43 +1156,50 @@ bp_resolve2_kernel(const uint32_t* __restrict__ order, const uint32_t* __restric
 //     cannot be allocated falls back to the last capacity that could (or to
 //     none: every long payload then takes the wave kernel), never an error.
 namespace {
-inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+using namespace bpmd::bp;
+
+// bp_stats_kernel's target of segments per lane of the chip (2 / 4 / 8: C4
+// 8-way shard 10.3 / 9.1 / 9.3 ms, C5 92 / 96 / 100 GiB/s,
+// profiles/r04zp_bp_segs_per_lane.log)
+constexpr uint32_t SEGS_PER_LANE = 4;
+// bp_scan_kernel pass 2 searches every n-th pending region; 1: the stride it
+// works out per payload (4 everywhere measured C4 8-way Beast shard 16.6 ->
+// 17.8 ms, C5 17.6 -> 15.7 ms, profiles/r05j_ab_compact_canon.log)
+constexpr uint32_t DYN_STRIDE = 1;
+
 struct BpCaps {
     int dev;
     hipStream_t s;
-    unsigned long long tasks, words;   // decode workspace capacity
-    bpmd::bp::Totals* seen;            // pinned: the totals of the last call
-    hipEvent_t ev;                     // recorded after that copy
-    bool pending;                      // ev recorded, not yet consumed
-    bool sized;                        // capacity set (first call or reserve)
-    // after a workspace allocation failed: the capacity that could be had is
-    // a ceiling for the next `hold` calls (8, doubling with every failure up
-    // to 1024), so under memory pressure a call does not sync, free and fail
-    // to allocate again every time
-    unsigned long long ceil_tasks, ceil_words;
-    uint32_t hold, backoff;
+    Capacity cap;      // decode workspace capacity
+    Totals* seen;      // pinned: the totals of the last call
+    hipEvent_t ev;     // recorded after that copy
+    bool pending;      // ev recorded, not yet consumed
 };
 std::mutex g_bp_mu;
 std::vector<BpCaps> g_bp_caps;
 std::atomic<int> g_bp_fail{0};   // diagnostics: decode-workspace allocations to fail
-std::atomic<int> g_bp_skim{-1};  // the skim: -1 from BPMD_BP_SKIM, 0 off, 1 on
 
-uint8_t* dw_alloc(hipStream_t s, size_t bytes)
+constexpr int E_UNKNOWN = (int)hipErrorUnknown, E_MEMORY = (int)hipErrorOutOfMemory;
+inline bool ok(hipError_t e) { return e == hipSuccess; }
+inline bool launched() { return ok(hipGetLastError()); }   // the launches since the last check were accepted
+
+uint8_t* dw_alloc(hipStream_t s, Need cap, uint32_t n)
 {
     if (g_bp_fail.load() > 0 && g_bp_fail.fetch_sub(1) > 0) return nullptr;
-    return bpmd::scratch_block(s, bytes, bpmd::SCR_BP_DECODE);
+    return bpmd::scratch_block(s, dw_bytes(cap, n), bpmd::SCR_BP_DECODE);
 }
 
 // the entry of (device, stream), created zeroed; nullptr when the pinned
-// totals or the event cannot be made.  Caller holds g_bp_mu.
+// totals or the event cannot be made.  Caller holds g_bp_mu, and looks the
+// entry up again in every locked section: entries move when streams come and go.
 BpCaps* caps_for(int dev, hipStream_t s)
 {
     for (auto& e : g_bp_caps)
         if (e.dev == dev && e.s == s) return &e;
-    BpCaps e{dev, s, 0, 0, nullptr, nullptr, false, false, 0, 0, 0, 8};
-    if (hipHostMalloc((void**)&e.seen, sizeof(bpmd::bp::Totals), hipHostMallocDefault) != hipSuccess) return nullptr;
+    BpCaps e{dev, s, Capacity{}, nullptr, nullptr, false};
+    if (!ok(hipHostMalloc((void**)&e.seen, sizeof(Totals), hipHostMallocDefault))) return nullptr;
     e.seen->tasks = e.seen->words = 0;
-    if (hipEventCreateWithFlags(&e.ev, hipEventDisableTiming) != hipSuccess) {
+    if (!ok(hipEventCreateWithFlags(&e.ev, hipEventDisableTiming))) {
         (void)hipHostFree(e.seen);
         return nullptr;
     }
@@ -1684,55 +1207,35 @@ BpCaps* caps_for(int dev, hipStream_t s)
     return &g_bp_caps.back();
 }
 
-// decode workspace layout for a capacity (n: the batch's message count):
-// tasks, results, fallback list, region map, marks, the resolve's chains
-// (output start and slot of every segment on a payload's chain, in chain
-// order at the payload's first task; per payload: chain length, output
-// length, status), symbols
-struct DwLayout {
-    size_t tasks, res, fb, map, mark, chp, chs, pay, sym, bytes;
-    DwLayout(unsigned long long nt, unsigned long long words, uint32_t n)
-    {
-        using namespace bpmd::bp;
-        tasks = 0;
-        res = al256(tasks + sizeof(SegTask) * nt);
-        fb = al256(res + sizeof(SegRes) * nt);
-        map = al256(fb + 4ull * n);
-        mark = al256(map + 4ull * nt);
-        chp = al256(mark + 4ull * n);
-        chs = al256(chp + 4ull * nt);
-        pay = al256(chs + 8ull * nt);
-        sym = al256(pay + sizeof(PayRes) * (size_t)n);
-        bytes = al256(sym + 2ull * (words + SYM_GUARD + 64));
-    }
-};
-inline size_t dw_bytes(unsigned long long tasks, unsigned long long words, uint32_t n)
+// grow_to with the device's free memory, asked for only when the capacity
+// would move.  Caller holds g_bp_mu.
+void grow(BpCaps* c, Need want)
 {
-    return DwLayout(tasks, words, n).bytes;
+    size_t fr = 0, tot = 0;
+    const bool known = grows(c->cap, want) && ok(hipMemGetInfo(&fr, &tot));
+    grow_to(c->cap, want, known ? fr : FREE_UNKNOWN);
 }
 
-// a capacity of t tasks and w words plus a quarter, within half the free memory
-void grow_to(BpCaps* c, unsigned long long t, unsigned long long w)
+// The decode workspace (SCR_BP_DECODE) for the capacity *cap.  A block that
+// cannot be had: the capacity it replaces, else none; *cap is what was had.
+// nullptr: not even the lists of an empty capacity.
+uint8_t* decode_workspace(int dev, hipStream_t s, uint32_t n, Need* cap)
 {
-    unsigned long long nt = c->tasks, nw = c->words;
-    if (t > nt) nt = t + t / 4;
-    if (w > nw) nw = w + w / 4;
-    if (nt > 0xffffffffull) nt = 0xffffffffull;
-    size_t fr = 0, tot = 0;
-    if ((nt != c->tasks || nw != c->words) && hipMemGetInfo(&fr, &tot) == hipSuccess) {
-        // per task: the task, its result, the region map word and the
-        // resolve's chain entries (DwLayout chp 4 B, chs 8 B)
-        const unsigned long long budget = fr / 2,
-                                 per_task = sizeof(bpmd::bp::SegTask) + sizeof(bpmd::bp::SegRes) + 4 + 4 + 8;
-        if (nt * per_task > budget) nt = budget / per_task;
-        if (2 * nw + nt * per_task > budget) nw = (budget - nt * per_task) / 2;
+    uint8_t* dw = dw_alloc(s, *cap, n);
+    if (dw) return dw;
+    (void)hipGetLastError();   // clear the allocation error
+    {
+        std::lock_guard<std::mutex> lk(g_bp_mu);
+        BpCaps* c = caps_for(dev, s);
+        *cap = c ? alloc_failed(c->cap, *cap) : Need{0, 0};
     }
-    if (c->hold) {
-        nt = nt < c->ceil_tasks ? nt : c->ceil_tasks;
-        nw = nw < c->ceil_words ? nw : c->ceil_words;
+    while (!(dw = dw_alloc(s, *cap, n))) {
+        (void)hipGetLastError();
+        if (!alloc_retry(*cap)) return nullptr;
     }
-    c->tasks = nt > c->tasks ? nt : c->tasks;
-    c->words = nw > c->words ? nw : c->words;
+    std::lock_guard<std::mutex> lk(g_bp_mu);
+    if (BpCaps* c = caps_for(dev, s)) alloc_settled(c->cap, *cap);
+    return dw;
 }
 }  // namespace
 
@@ -1740,7 +1243,7 @@ void grow_to(BpCaps* c, unsigned long long t, unsigned long long w)
 void bpmd::bp_release(hipStream_t s)
 {
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return;
+    if (!ok(hipGetDevice(&dev))) return;
     std::lock_guard<std::mutex> lk(g_bp_mu);
     for (size_t i = 0; i < g_bp_caps.size(); ++i)
         if (g_bp_caps[i].dev == dev && g_bp_caps[i].s == s) {
@@ -1753,231 +1256,144 @@ void bpmd::bp_release(hipStream_t s)
         }
 }
 
-// bpmd_inflate_reserve (pmd_capi.hip): a capacity for batches whose long
-// payloads total at most in_bytes of input, out_bytes of output capacity and
-// msgs payloads -- bp_stats_kernel's bounds: regions of >= R_MIN bytes, at
-// most one more per payload; slot words 2 (len + regions) x 1.25 x
-// min(cap / len, 4) + SLACK per region + the guard per payload.
+// bpmd_inflate_reserve (pmd_capi.hip): the capacity of reserve_need, no wait
 int bpmd::bp_reserve(hipStream_t s, unsigned long long in_bytes, unsigned long long out_bytes,
                      unsigned long long msgs)
 {
-    using namespace bpmd::bp;
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return (int)hipErrorNoDevice;
-    const unsigned long long t = in_bytes / R_MIN + msgs;
-    // (bp_stats_kernel: slots of 3 (len + regions) x F16 symbols, F16 = 1.25 x cap / len)
-    const unsigned long long w = (15 * out_bytes) / 4 + (15ull + SLACK) * t + (SYM_GUARD + 64ull) * msgs;
+    if (!ok(hipGetDevice(&dev))) return (int)hipErrorNoDevice;
     std::lock_guard<std::mutex> lk(g_bp_mu);
     BpCaps* c = caps_for(dev, s);
-    if (!c) return (int)hipErrorOutOfMemory;
-    grow_to(c, t, w);
-    c->sized = true;
+    if (!c) return E_MEMORY;
+    grow(c, reserve_need(in_bytes, out_bytes, msgs));
+    c->cap.sized = true;
     return 0;
 }
 
 int bpmd::inflate_bp(const Batch& b, uint32_t raw, const uint32_t* order, const uint32_t* nlong, hipStream_t s)
 {
-    using namespace bpmd::bp;
     const auto& [in, in_off, in_len, n, out, out_off, out_cap, out_len, status] = b;
     if (n == 0) return 0;
     int dev = 0;
     (void)hipGetDevice(&dev);
-    const int cus = cu_count();
-    // this stream's capacity, grown to what an earlier call needed
-    unsigned long long cap_tasks = 0, cap_words = 0;
+    const uint32_t cus = (uint32_t)cu_count();
+
+    // capacity in: this stream's, grown to what an earlier call needed
+    Need cap = {0, 0};
     Totals* seen = nullptr;
     hipEvent_t ev = nullptr;
     bool cold = false;
     {
         std::lock_guard<std::mutex> lk(g_bp_mu);
         BpCaps* c = caps_for(dev, s);
-        if (!c) return (int)hipErrorOutOfMemory;
-        if (c->hold) --c->hold;   // the ceiling lifts after `hold` calls
-        if (c->pending && hipEventQuery(c->ev) == hipSuccess) {
+        if (!c) return E_MEMORY;
+        begin_call(c->cap);
+        if (c->pending && ok(hipEventQuery(c->ev))) {
             c->pending = false;
-            grow_to(c, c->seen->tasks, c->seen->words);
+            grow(c, {c->seen->tasks, c->seen->words});
         }
-        cold = !c->sized;
-        cap_tasks = c->tasks;
-        cap_words = c->words;
+        cold = !c->cap.sized;
+        cap = {c->cap.tasks, c->cap.words};
         seen = c->seen;
         ev = c->ev;
     }
-    // per-payload workspace (SCR_BP_STATS): stats, regions, words, their
-    // exclusive sums, totals, fit, queues, scan temp
+
+    // stats.  Per-payload workspace (SCR_BP_STATS): stats, regions, words,
+    // their exclusive sums, totals, queues, scan temp
     size_t tmp1 = 0, tmp2 = 0;
-    if (hipcub::DeviceScan::ExclusiveSum(nullptr, tmp1, (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)n, s) !=
-            hipSuccess ||
-        hipcub::DeviceScan::ExclusiveSum(nullptr, tmp2, (const unsigned long long*)nullptr,
-                                         (unsigned long long*)nullptr, (int)n, s) != hipSuccess)
-        return (int)hipErrorUnknown;
+    if (!ok(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp1, (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)n, s)) ||
+        !ok(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp2, (const unsigned long long*)nullptr,
+                                             (unsigned long long*)nullptr, (int)n, s)))
+        return E_UNKNOWN;
     const size_t o_st = 0, o_reg = al256(o_st + sizeof(Stat) * (size_t)n), o_tb = al256(o_reg + 4ull * n),
                  o_w = al256(o_tb + 4ull * n), o_wb = al256(o_w + 8ull * n), o_tot = al256(o_wb + 8ull * n),
                  o_q = al256(o_tot + sizeof(Totals)), o_tmp = al256(o_q + 64),
                  sz = al256(o_tmp + (tmp1 > tmp2 ? tmp1 : tmp2));
-    // q: [0] scan queue, [1] resolve queue, [2] fallback count, [3] seg queue,
-    // [4-5] long bytes, [6] payloads that fit, [7] their tasks
     uint8_t* ws = scratch_block(s, sz, SCR_BP_STATS);
-    if (!ws) return (int)hipErrorOutOfMemory;
+    if (!ws) return E_MEMORY;
     Stat* st = (Stat*)(ws + o_st);
     uint32_t* reg = (uint32_t*)(ws + o_reg);
     uint32_t* tbase = (uint32_t*)(ws + o_tb);
     unsigned long long* words = (unsigned long long*)(ws + o_w);
     unsigned long long* wbase = (unsigned long long*)(ws + o_wb);
     Totals* dtot = (Totals*)(ws + o_tot);
-    uint32_t* q = (uint32_t*)(ws + o_q);
     void* tmp = ws + o_tmp;
+    // q: [0] scan queue, [1] resolve queue, [2] fallback count, [3] seg queue,
+    // [4-5] long bytes, [6] payloads that fit, [7] their tasks
+    uint32_t* q = (uint32_t*)(ws + o_q);
+    uint32_t *resolve_q = q + 1, *fb_count = q + 2, *seg_q = q + 3, *fit = q + 6, *fit_tasks = q + 7;
     unsigned long long* total = (unsigned long long*)(q + 4);
-    uint32_t* fit = q + 6;
-    if (hipMemsetAsync(q, 0, 64, s) != hipSuccess) return (int)hipErrorUnknown;
+    if (!ok(hipMemsetAsync(q, 0, 64, s))) return E_UNKNOWN;
     hipLaunchKernelGGL(bp_sum_kernel, dim3(n / 256 + 1 < 1024 ? n / 256 + 1 : 1024), dim3(256), 0, s, in_len, order,
                        nlong, n, total);
-    // BPMD_BP_SEGS (diagnostics): target segments per lane of the chip
-    // (0: the default 4.  2 / 4 / 8: C4 8-way shard 10.3 / 9.1 / 9.3 ms, C5 92 / 96 / 100 GiB/s)
-    static const uint32_t segs_env = env_uint("BPMD_BP_SEGS", 0u), segs = segs_env ? segs_env : 4u;
     hipLaunchKernelGGL(bp_stats_kernel, dim3((n + 255) / 256), dim3(256), 0, s, in_len, out_cap, order, nlong, n, total,
-                       256u * (uint32_t)cus, segs, st, reg, words);
-    if (hipGetLastError() != hipSuccess) return (int)hipErrorUnknown;
+                       256u * cus, SEGS_PER_LANE, st, reg, words);
+    if (!launched()) return E_UNKNOWN;
     size_t t1 = tmp1, t2 = tmp2;
-    if (hipcub::DeviceScan::ExclusiveSum(tmp, t1, reg, tbase, (int)n, s) != hipSuccess ||
-        hipcub::DeviceScan::ExclusiveSum(tmp, t2, words, wbase, (int)n, s) != hipSuccess)
-        return (int)hipErrorUnknown;
+    if (!ok(hipcub::DeviceScan::ExclusiveSum(tmp, t1, reg, tbase, (int)n, s)) ||
+        !ok(hipcub::DeviceScan::ExclusiveSum(tmp, t2, words, wbase, (int)n, s)))
+        return E_UNKNOWN;
     if (cold) {
         // the stream's first call: its own totals, read back once
         hipLaunchKernelGGL(bp_totals_kernel, dim3(1), dim3(64), 0, s, reg, tbase, words, wbase, n, dtot);
-        if (hipGetLastError() != hipSuccess ||
-            hipMemcpyAsync(seen, dtot, sizeof(Totals), hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess)
-            return (int)hipErrorUnknown;
+        if (!launched() || !ok(hipMemcpyAsync(seen, dtot, sizeof(Totals), hipMemcpyDeviceToHost, s)) ||
+            !ok(hipStreamSynchronize(s)))
+            return E_UNKNOWN;
         std::lock_guard<std::mutex> lk(g_bp_mu);
         BpCaps* c = caps_for(dev, s);
-        if (!c) return (int)hipErrorOutOfMemory;
-        grow_to(c, seen->tasks, seen->words);
-        c->sized = true;
-        cap_tasks = c->tasks;
-        cap_words = c->words;
+        if (!c) return E_MEMORY;
+        grow(c, {seen->tasks, seen->words});
+        c->cap.sized = true;
+        cap = {c->cap.tasks, c->cap.words};
     }
-    // decode workspace (SCR_BP_DECODE), sized by the capacity: tasks,
-    // results, fallback list, region map, marks, symbols.  A block that
-    // cannot be had: the capacity it replaces, else none.
-    uint8_t* dw = dw_alloc(s, dw_bytes(cap_tasks, cap_words, n));
-    if (!dw) {
-        (void)hipGetLastError();   // clear the allocation error
-        unsigned long long pt = 0, pw = 0;
-        {
-            std::lock_guard<std::mutex> lk(g_bp_mu);
-            BpCaps* c = caps_for(dev, s);
-            if (c) {
-                pt = c->tasks = c->tasks == cap_tasks ? c->tasks / 2 : c->tasks;
-                pw = c->words = c->words == cap_words ? c->words / 2 : c->words;
-            }
-        }
-        cap_tasks = pt;
-        cap_words = pw;
-        for (;;) {
-            if (cap_words < (1ull << 16)) cap_tasks = cap_words = 0;
-            dw = dw_alloc(s, dw_bytes(cap_tasks, cap_words, n));
-            if (dw) break;
-            (void)hipGetLastError();
-            if (cap_words == 0) return (int)hipErrorOutOfMemory;   // not even the lists
-            cap_tasks /= 2;
-            cap_words /= 2;
-        }
-        std::lock_guard<std::mutex> lk(g_bp_mu);
-        BpCaps* c = caps_for(dev, s);
-        if (c) {
-            c->tasks = cap_tasks;
-            c->words = cap_words;
-            c->ceil_tasks = cap_tasks;
-            c->ceil_words = cap_words;
-            c->hold = c->backoff;
-            c->backoff = c->backoff < 1024 ? 2 * c->backoff : 1024u;
-        }
-    }
-    const DwLayout D(cap_tasks, cap_words, n);
+
+    // fit: the decode workspace for the capacity, and the payloads it takes
+    uint8_t* dw = decode_workspace(dev, s, n, &cap);
+    if (!dw) return E_MEMORY;
+    const DwLayout D(cap, n);
     SegTask* tasks = (SegTask*)(dw + D.tasks);
     SegRes* res = (SegRes*)(dw + D.res);
     uint32_t* fb = (uint32_t*)(dw + D.fb);
-    uint16_t* sym = (uint16_t*)(dw + D.sym);
     uint32_t* rmap = (uint32_t*)(dw + D.map);
     uint32_t* marked = (uint32_t*)(dw + D.mark);
-    uint32_t* chp = (uint32_t*)(dw + D.chp);
-    uint64_t* chs = (uint64_t*)(dw + D.chs);
-    PayRes* pay = (PayRes*)(dw + D.pay);
-    if (hipMemsetAsync(marked, 0, 4ull * n, s) != hipSuccess) return (int)hipErrorUnknown;
-    hipLaunchKernelGGL(bp_fit_kernel, dim3(1), dim3(256), 0, s, nlong, reg, tbase, words, wbase, n, cap_tasks,
-                       cap_words, order, fit, dtot, fb, q + 2);
+    uint16_t* sym = (uint16_t*)(dw + D.sym);
+    if (!ok(hipMemsetAsync(marked, 0, 4ull * n, s))) return E_UNKNOWN;
+    hipLaunchKernelGGL(bp_fit_kernel, dim3(1), dim3(256), 0, s, nlong, reg, tbase, words, wbase, n, cap.tasks,
+                       cap.words, order, fit, dtot, fb, fb_count);
     // the totals for a later call (pinned, no wait here); the event counts
     // only once it is recorded
-    if (hipGetLastError() != hipSuccess ||
-        hipMemcpyAsync(seen, dtot, sizeof(Totals), hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipEventRecord(ev, s) != hipSuccess)
-        return (int)hipErrorUnknown;
+    if (!launched() || !ok(hipMemcpyAsync(seen, dtot, sizeof(Totals), hipMemcpyDeviceToHost, s)) ||
+        !ok(hipEventRecord(ev, s)))
+        return E_UNKNOWN;
     {
         std::lock_guard<std::mutex> lk(g_bp_mu);
-        BpCaps* c = caps_for(dev, s);
-        if (c) c->pending = true;
+        if (BpCaps* c = caps_for(dev, s)) c->pending = true;
     }
+
     // scan: one wave per region, SCAN_WAVES waves per workgroup, ~3
     // workgroups per CU by LDS; then the slots, one wave per payload
     hipLaunchKernelGGL(bp_region_map_kernel, dim3((n + 255) / 256), dim3(256), 0, s, fit, reg, tbase, rmap);
-    const uint32_t scan_wgs = 3u * cus;
-    // BPMD_BP_DYN_STRIDE: pass 2 searches every n-th pending region (default
-    // 1; 4 measured C4 8-way Beast shard 16.6 -> 17.8 ms, C5 17.6 -> 15.7 ms,
-    // profiles/r05j_ab_compact_canon.log)
-    // (0 or 1: the per-payload stride, bp_scan_kernel)
-    static const uint32_t stride_env = env_uint("BPMD_BP_DYN_STRIDE", 0u), dyn_stride = stride_env ? stride_env : 1u;
-    hipLaunchKernelGGL(bp_scan_kernel<false>, dim3(scan_wgs), dim3(64 * SCAN_WAVES), 0, s, in, in_off, in_len, order,
-                       rmap, fit + 1, st, tbase, tasks, marked, dyn_stride);
-    // the skim (payloads without sync markers), then pass 2 on the regions no
-    // walk reached (BPMD_BP_SKIM=1; off by default: see the A/B in DESIGN 4.1d)
-    int skim_mode = g_bp_skim.load();
-    if (skim_mode < 0) {
-        const char* e = getenv("BPMD_BP_SKIM");
-        skim_mode = e && e[0] == '1' ? 1 : 0;
-        g_bp_skim.store(skim_mode);
-    }
-    const bool skim = skim_mode == 1;
-    if (skim)
-        hipLaunchKernelGGL(bp_skim_kernel, dim3(4u * cus), dim3(256), 0, s, in, in_off, in_len, order, rmap, fit + 1, st,
-                           tbase, tasks, marked);
-    hipLaunchKernelGGL(bp_scan_kernel<true>, dim3(scan_wgs), dim3(64 * SCAN_WAVES), 0, s, in, in_off, in_len, order,
-                       rmap, fit + 1, st, tbase, tasks, marked, dyn_stride);
-    hipLaunchKernelGGL(bp_slots_kernel, dim3(4u * cus), dim3(256), 0, s, in_len, order, fit, st, tbase,
-                       wbase, tasks);
-    if (hipGetLastError() != hipSuccess) return (int)hipErrorUnknown;
-    // segments: a work queue over the device-side task count
-    const uint32_t wgs = 4u * cus;
-    int e = inflate_lane3_seg(in, in_off, in_len, (uint32_t)cap_tasks, tasks, sym, res, raw, q + 3, wgs, s, fit + 1);
-    if (e) return e;
-    // resolve: the serial walk per payload (default), or the segment-parallel
-    // form (BPMD_BP_RESOLVE=parallel; measured slower: a reference in
-    // deflated JSON usually points at a byte that was itself copied from the
-    // segment before, and so on back to the payload's first segment, so the
-    // chase through symbols runs one hop per earlier segment -- C4 8-way
-    // shard 8.6 -> 14.7 ms, profiles/r05e_resolve_ab.log)
-    static const bool serial_resolve = [] {
-        const char* e = getenv("BPMD_BP_RESOLVE");
-        return !(e && !strcmp(e, "parallel"));
-    }();
-    if (serial_resolve) {
-        hipLaunchKernelGGL(bp_resolve_kernel, dim3(8u * cus), dim3(256), 0, s, in, in_off, order, fit, tbase, tasks, res,
-                           sym, out, out_off, out_cap, out_len, status, raw, fb, q + 2, q + 1, st);
-        if (hipGetLastError() != hipSuccess) return (int)hipErrorUnknown;
-    } else {
-        hipLaunchKernelGGL(bp_chain_kernel, dim3(n / 256 + 1), dim3(256), 0, s, order, fit, tbase, tasks, res, out_cap,
-                           raw, st, chp, chs, pay, out_len, status, fb, q + 2);
-        hipLaunchKernelGGL(bp_resolve2_kernel, dim3(8u * cus), dim3(RES_THREADS), 0, s, order, fit, tbase, sym, out,
-                           out_off, out_cap, out_len, status, raw, chp, chs, pay, q + 1);
-        if (hipGetLastError() != hipSuccess) return (int)hipErrorUnknown;
-    }
-    // payloads over the capacity or whose output outgrew the slots: the wave
-    // kernel, from the list
-    return inflate_wave_ordered(b, raw, nullptr, fb, q + 2, s);
-}
+    hipLaunchKernelGGL(bp_scan_kernel<false>, dim3(3u * cus), dim3(64 * SCAN_WAVES), 0, s, in, in_off, in_len, order,
+                       rmap, fit_tasks, st, tbase, tasks, marked, DYN_STRIDE);
+    hipLaunchKernelGGL(bp_scan_kernel<true>, dim3(3u * cus), dim3(64 * SCAN_WAVES), 0, s, in, in_off, in_len, order,
+                       rmap, fit_tasks, st, tbase, tasks, marked, DYN_STRIDE);
+    hipLaunchKernelGGL(bp_slots_kernel, dim3(4u * cus), dim3(256), 0, s, in_len, order, fit, st, tbase, wbase, tasks);
+    if (!launched()) return E_UNKNOWN;
 
-// the fixed-block skim on (1) or off (0) for the following calls (tests, A/B)
-extern "C" void bpmd_diag_set_bp_skim(int on) { g_bp_skim.store(on ? 1 : 0); }
+    // segments: a work queue over the device-side task count
+    if (int e = inflate_lane3_seg(in, in_off, in_len, (uint32_t)cap.tasks, tasks, sym, res, raw, seg_q, 4u * cus, s,
+                                  fit_tasks))
+        return e;
+
+    // resolve: the serial walk per payload
+    hipLaunchKernelGGL(bp_resolve_kernel, dim3(8u * cus), dim3(256), 0, s, in, in_off, order, fit, tbase, tasks, res,
+                       sym, out, out_off, out_cap, out_len, status, raw, fb, fb_count, resolve_q, st);
+    if (!launched()) return E_UNKNOWN;
+
+    // fallback: payloads over the capacity or whose output outgrew the slots
+    // go to the wave kernel, from the list
+    return inflate_wave_ordered(b, raw, nullptr, fb, fb_count, s);
+}
 
 // diagnostics (tests): the next k decode-workspace allocations fail
 extern "C" void bpmd_diag_bp_fail_alloc(int k) { g_bp_fail.store(k); }
@@ -1988,15 +1404,15 @@ extern "C" void bpmd_diag_bp_fail_alloc(int k) { g_bp_fail.store(k); }
 extern "C" int bpmd_diag_bp_caps(hipStream_t s, unsigned long long* out5)
 {
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return -1;
+    if (!ok(hipGetDevice(&dev))) return -1;
     std::lock_guard<std::mutex> lk(g_bp_mu);
     for (auto& e : g_bp_caps)
         if (e.dev == dev && e.s == s) {
-            out5[0] = e.tasks;
-            out5[1] = e.words;
-            out5[2] = e.ceil_tasks;
-            out5[3] = e.ceil_words;
-            out5[4] = e.hold;
+            out5[0] = e.cap.tasks;
+            out5[1] = e.cap.words;
+            out5[2] = e.cap.ceil_tasks;
+            out5[3] = e.cap.ceil_words;
+            out5[4] = e.cap.hold;
             return 0;
         }
     return -1;
@@ -2004,18 +1420,19 @@ extern "C" int bpmd_diag_bp_caps(hipStream_t s, unsigned long long* out5)
 
 extern "C" int bpmd_diag_bp_fallback(uint32_t* out8)
 {
-    return hipMemcpyFromSymbol(out8, HIP_SYMBOL(bpmd::bp::g_bp_fb), sizeof(uint32_t) * 8) == hipSuccess ? 0 : -1;
+    return ok(hipMemcpyFromSymbol(out8, HIP_SYMBOL(bpmd::bp::g_bp_fb), sizeof(uint32_t) * 8)) ? 0 : -1;
 }
 
 // diagnostics: the 12 counters of g_bp_diag (out[12]); reset after reading
 extern "C" int bpmd_diag_bp_counters(unsigned long long* out, int reset)
 {
     unsigned long long v[12] = {};
-    if (hipMemcpyFromSymbol(v, HIP_SYMBOL(bpmd::bp::g_bp_diag), sizeof v) != hipSuccess) return -1;
+    if (!ok(hipMemcpyFromSymbol(v, HIP_SYMBOL(bpmd::bp::g_bp_diag), sizeof v))) return -1;
     for (int i = 0; i < 12; ++i) out[i] = v[i];
     if (reset) {
         const unsigned long long z[12] = {};
-        if (hipMemcpyToSymbol(HIP_SYMBOL(bpmd::bp::g_bp_diag), z, sizeof z) != hipSuccess) return -1;
+        if (!ok(hipMemcpyToSymbol(HIP_SYMBOL(bpmd::bp::g_bp_diag), z, sizeof z))) return -1;
     }
     return 0;
 }
+

@@ -248,7 +248,7 @@ def test_foreign_payload_with_one_early_flush():
 
 def test_stored_block_ending_in_the_last_region():
     """the last region of a payload also takes the remainder past
-    regions * R (region_of), so a stored block whose data ends inside it, past
+    regions * R (bp_stats_kernel), so a stored block whose data ends inside it, past
     (k + 1) * R, may be followed by a block start in that region.  Pass 2 used
     to take (k + 1) * R as the region's end (skipping it as "inside the stored
     data") and searched only up to there; it now uses the real end, and the
@@ -450,10 +450,10 @@ def test_failed_workspace_allocation_falls_back():
 def test_deep_reference_chains(mode):
     """A 1 KiB pattern repeated with 5-10 % of its bytes changed each time:
     most bytes copy the byte one period back, which was itself copied, so a
-    reference crosses many segments before it reaches a literal.  Chains
-    deeper than the resolve's hop limit are finished segment by segment
-    (pmd_inflate_bp.hip bp_resolve2_kernel pass 3); every byte must equal the
-    oracle's."""
+    reference crosses many segments before it reaches a literal.  The resolve
+    takes the segments in stream order, each reference reading the byte the
+    earlier ones wrote (pmd_inflate_bp.hip bp_resolve_kernel); every byte must
+    equal the oracle's."""
     rng = random.Random(0xDEE9)
     payloads, caps = [], []
     for size, rate in ((120000, 0.05), (65536, 0.10), (200000, 0.02)):
@@ -472,13 +472,12 @@ def test_deep_reference_chains(mode):
 
 
 @pytest.mark.parametrize("level", [1, 6])
-def test_fixed_block_skim(mode, level):
-    """The fixed-block skim (off by default; bpmd_diag_set_bp_skim): Beast's
-    near-random payloads are runs of stored and fixed blocks, and the walks
-    from pass 1's stored candidates record every block start they pass.
-    Results must stay the serial decoder's, including capacity cuts and
-    corrupted payloads (a walk only ever adds candidates)."""
-    pmd = _pmd()
+def test_beast_stored_and_fixed_runs(mode, level):
+    """Beast's near-random payloads are runs of stored and fixed blocks (the
+    scan finds the stored blocks in pass 1 and fixed-block starts after a
+    fixed block in pass 2), mixed here with text.  Results must stay the
+    serial decoder's, including capacity cuts and corrupted payloads (a
+    candidate only ever cuts the serial decode)."""
     rng = random.Random(0x5C1 + level)
     payloads, caps = [], []
     for i in range(40):
@@ -490,9 +489,5 @@ def test_fixed_block_skim(mode, level):
         q = bytearray(payloads[i])
         q[rng.randrange(len(q))] ^= 1 << rng.randrange(8)
         payloads[i] = bytes(q)
-    pmd.lib().bpmd_diag_set_bp_skim(1)
-    try:
-        _check(payloads, caps)
-        _check(payloads, caps, raw=True)
-    finally:
-        pmd.lib().bpmd_diag_set_bp_skim(0)
+    _check(payloads, caps)
+    _check(payloads, caps, raw=True)
