@@ -360,10 +360,8 @@ int inflate_impl(const bpmd_cfg* cfg, const Batch& b, const uint32_t* key, const
     return e ? BPMD_R_HIP_ERROR : BPMD_R_OK;
 }
 
-// chunk_bound >= 0 (with hist): at least the batch's chunk count, so the
-// deflater does not read it back (bpmd::deflate_takeover_bounded)
-int deflate_impl(const bpmd_cfg* cfg, const Batch& b, const uint32_t* key, const uint32_t* hist, void* stream,
-                 int64_t chunk_bound = -1)
+// o: the caller's mask keys, history lengths and chunk-count source; the rest is filled in from cfg
+int deflate_impl(const bpmd_cfg* cfg, const Batch& b, DeflateOpts o, void* stream)
 {
     if (!cfg) return BPMD_R_INVALID_ARGUMENT;
     // deflate_stream.ipp:235-253: level -1 means 6; windowBits 8 becomes 9;
@@ -384,12 +382,12 @@ int deflate_impl(const bpmd_cfg* cfg, const Batch& b, const uint32_t* key, const
     std::lock_guard<std::mutex> launch(*mu);
     if (cfg->flags & BPMD_F_EXACT) {
         // the reference's own algorithm, message by message (pmd_deflate_exact.hip)
-        if (hist) return BPMD_R_INVALID_ARGUMENT;
-        return deflate_exact(b, level, wbits, cfg->mem_level, cfg->strategy, key, s) ? BPMD_R_HIP_ERROR : BPMD_R_OK;
+        if (o.hist_len) return BPMD_R_INVALID_ARGUMENT;
+        const int e = deflate_exact(b, level, wbits, cfg->mem_level, cfg->strategy, o.mask_key, s);
+        return e ? BPMD_R_HIP_ERROR : BPMD_R_OK;
     }
-    int e = hist ? deflate_takeover(b, level, wbits, cfg->strategy, hist, s, chunk_bound)
-                 : deflate_keyed(b, level, wbits, cfg->strategy, key, s);
-    return e ? BPMD_R_HIP_ERROR : BPMD_R_OK;
+    o.level = level, o.window_bits = wbits, o.strategy = cfg->strategy;
+    return deflate(b, o, s) ? BPMD_R_HIP_ERROR : BPMD_R_OK;
 }
 
 }  // namespace
@@ -409,7 +407,7 @@ extern "C" int bpmd_deflate_batch(const bpmd_cfg* cfg, const uint8_t* d_in, cons
                                   uint32_t* d_out_len, int32_t* d_status, void* stream)
 {
     const Batch b{d_in, d_in_off, d_in_len, n_msgs, d_out, d_out_off, d_out_cap, d_out_len, d_status};
-    return deflate_impl(cfg, b, nullptr, nullptr, stream);
+    return deflate_impl(cfg, b, DeflateOpts(), stream);
 }
 
 // ------------------------------------------------ frame passes (§8(f) N1)
@@ -506,7 +504,9 @@ extern "C" int bpmd_write_batch(const bpmd_cfg* cfg, const uint8_t* d_in, const 
                                 int32_t* d_status, void* stream)
 {
     const Batch b{d_in, d_in_off, d_in_len, n_msgs, d_out, d_out_off, d_out_cap, d_out_len, d_status};
-    return deflate_impl(cfg, b, d_key, nullptr, stream);
+    DeflateOpts o;
+    o.mask_key = d_key;
+    return deflate_impl(cfg, b, o, stream);
 }
 
 // ---------------------------------------------- context takeover (§8(f) N3)
@@ -528,14 +528,16 @@ extern "C" int bpmd_deflate_takeover_batch(const bpmd_cfg* cfg, const uint8_t* d
 {
     const Batch b{d_in, d_in_off, d_in_len, n_msgs, d_out, d_out_off, d_out_cap, d_out_len, d_status};
     if (n_msgs && !d_hist_len) return BPMD_R_INVALID_ARGUMENT;
-    return deflate_impl(cfg, b, nullptr, d_hist_len, stream);
+    DeflateOpts o;
+    o.hist_len = d_hist_len;
+    return deflate_impl(cfg, b, o, stream);
 }
 
-int bpmd::deflate_takeover_bounded(const bpmd_cfg* cfg, const Batch& b, const uint32_t* hist_len, uint64_t chunk_bound,
-                                   hipStream_t stream)
+int bpmd::deflate_takeover_bounded(const bpmd_cfg* cfg, const Batch& b, const DeflateOpts& opts, hipStream_t stream)
 {
-    if ((b.n && !hist_len) || chunk_bound > 0xFFFFFFFFull) return BPMD_R_INVALID_ARGUMENT;
-    return deflate_impl(cfg, b, nullptr, hist_len, stream, (int64_t)chunk_bound);
+    if ((b.n && !opts.hist_len) || opts.chunks.kind != dfl::ChunkSource::BOUND || opts.chunks.chunks > 0xFFFFFFFFull)
+        return BPMD_R_INVALID_ARGUMENT;
+    return deflate_impl(cfg, b, opts, stream);
 }
 
 extern "C" int bpmd_slide_batch(uint8_t* d_buf, const uint64_t* d_base, const uint32_t* d_pos, const uint32_t* d_keep,

@@ -45,12 +45,12 @@
 #include "pmd_common.h"
 #include "wave_util.h"
 #include "lz_core.h"
+#include "deflate_plan.h"
 #include "pmd_internal.h"
 
 namespace bpmd {
 namespace dfl {
 
-constexpr unsigned CHUNK = 4096;
 constexpr unsigned HB = 11;
 constexpr unsigned HSIZE = 1u << HB;
 #ifndef BPMD_MIN_SEG
@@ -774,6 +774,10 @@ struct MsgOut {
     uint32_t key;      // masking key, 0 = unmasked: payload byte j ^= key >> 8 (j % 4) (mask.ipp:38-59)
     bool stored;       // the last chunk was written as a stored block
 };
+__device__ __forceinline__ MsgOut msg_out(uint8_t* dst, uint32_t cap, uint32_t key)
+{
+    return MsgOut{dst, cap, 0u, 0u, 0u, false, key, false};
+}
 
 __device__ __forceinline__ void put_bytes_global(MsgOut& o, const uint8_t* src_lds, unsigned ob, unsigned nbytes)
 {
@@ -1376,19 +1380,11 @@ deflate_kernel(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_o
     for (uint32_t i = blockIdx.x; i < n; i = next(i)) {
         const uint32_t len = in_len[i];
         if (len > CHUNK) continue;   // chunk-parallel path (deflate_chunks_kernel + stitch_kernel)
-        MsgOut o;
-        o.dst = out + out_off[i];
-        o.cap = out_cap[i];
-        o.opos = 0;
-        o.carry = 0;
-        o.cbits = 0;
-        o.overflow = false;
-        o.key = P.mask_key ? P.mask_key[i] : 0u;
-        o.stored = false;
+        MsgOut o = msg_out(out + out_off[i], out_cap[i], P.mask_key ? P.mask_key[i] : 0u);
         const uint8_t* msg = in + in_off[i];
         if (len) deflate_chunk<0>(S, msg, 0, len, 0u, P, o, pf);
         // Flush::sync's empty stored block header (000) + pad; 00 00 FF FF stripped
-        const unsigned tb = o.cbits + 3 > 8 ? 2u : 1u;
+        const unsigned tb = tail_bytes(o.cbits);
         if (!o.overflow && o.opos + tb > o.cap) o.overflow = true;
         if (lane == 0) {
             if (!o.overflow) {
@@ -1407,33 +1403,19 @@ deflate_kernel(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_o
 // ------------------------------------------------ chunk-parallel large messages
 // A message longer than one chunk (or any message of a context-takeover
 // batch) is encoded chunk by chunk IN PARALLEL: every 4 KiB chunk, with the
-// BPMD_CHUNK_HIST (2 KiB) of input before it as history, becomes one block of its own in a
-// scratch slot, starting at bit 0 (deflate_chunks_kernel); then one wave per
-// message stitches the blocks together at their bit offsets, applies the
-// client mask and appends Flush::sync's empty stored block header
-// (stitch_kernel).  A block's contents and its stored/fixed/dynamic choice do
-// not depend on where it starts, so the payload is bit for bit the one the
-// serial walk over the chunks would produce; only a stored block's padding to a byte
-// boundary depends on its start, and the stitch writes it there.
-constexpr unsigned SLOT = 4736;   // >= bpmd_deflate_upper_bound(CHUNK) + 2, 16-byte multiple
+// BPMD_CHUNK_HIST (2 KiB) of input before it as history, becomes one block of
+// its own in a scratch slot, starting at bit 0 (deflate_chunks_kernel); then
+// one wave per message puts the blocks at their bit offsets, masked
+// (stitch_kernel).  A block's contents and type do not depend on where it
+// starts, so the payload is bit for bit the serial walk's; only a stored block's
+// padding does, and the stitch writes it.  The rules: deflate_plan.h.
 constexpr int CHUNK_HIST = BPMD_CHUNK_HIST;   // (lz_core.h) history bytes before each chunk (and before a takeover message)
-
-// chunks of the chunk-parallel path: every chunk of a message with a history
-// window (all), else only messages over one chunk.  Shared with the host
-// (bpmd::deflate_chunks below: the count the per-stream deflater passes in).
-__host__ __device__ __forceinline__ uint32_t chunk_count(uint32_t len, bool all)
-{
-    return (all || len > CHUNK) ? (len + CHUNK - 1) / CHUNK : 0u;
-}
 
 struct ChunkCountOp {
     const uint32_t* len;
     uint32_t n;
     bool all;
-    __host__ __device__ uint32_t operator()(uint32_t i) const
-    {
-        return i < n ? ((all || len[i] > CHUNK) ? (len[i] + CHUNK - 1) / CHUNK : 0u) : 0u;
-    }
+    __host__ __device__ uint32_t operator()(uint32_t i) const { return i < n ? chunk_count(len[i], all) : 0u; }
 };
 
 __global__ void __launch_bounds__(256) count_chunks_kernel(const uint32_t* __restrict__ in_len, uint32_t n, uint32_t all,
@@ -1489,24 +1471,32 @@ deflate_chunks_kernel(const uint8_t* __restrict__ in, const uint64_t* __restrict
         const uint32_t c = k - first[i];
         const uint32_t len = in_len[i];
         const unsigned hist = P.hist_len ? (P.hist_len[i] < (unsigned)HIST ? P.hist_len[i] : (unsigned)HIST) : 0u;
-        MsgOut o;
-        o.dst = temp + (size_t)k * SLOT;
-        o.cap = SLOT;
-        o.opos = 0;
-        o.carry = 0;
-        o.cbits = 0;
-        o.overflow = false;
-        o.key = 0;
-        o.stored = false;
+        MsgOut o = msg_out(temp + (size_t)k * SLOT, SLOT, 0u);
         deflate_chunk<HIST>(S, in + in_off[i], c * CHUNK, len, hist, P, o, pf);
-        if (lane_id() == 0)
-            bits[k] = o.overflow ? 0xFFFFFFFFu : ((o.stored ? 0x80000000u : 0u) | (o.opos * 8 + o.cbits));
+        if (lane_id() == 0) bits[k] = chunk_word(o.overflow, o.stored, o.opos * 8 + o.cbits);
         wave_sync();
     }
     pf.flush();
 }
 
-// one wave per large message: its chunk blocks at their bit offsets
+__device__ __forceinline__ uint8_t key_byte(uint32_t key, uint32_t p) { return (uint8_t)(key >> (8 * (p & 3))); }
+// a stored block's 000 and pad: the partial byte cv, and a byte of zeros when the bits spill
+__device__ __forceinline__ void put_stored_head(uint8_t* o, const StoredSpan& s, uint32_t cv, uint32_t key, unsigned lane)
+{
+    if (lane == 0) {
+        o[s.at] = (uint8_t)cv ^ key_byte(key, s.at);
+        if (s.pay - s.at == 2) o[s.at + 1] = key_byte(key, s.at + 1);
+    }
+}
+
+// the marker: an empty stored block (000, pad, 00 00 FF FF); ~5 bytes per 4 KiB chunk
+__device__ __forceinline__ void put_marker(uint8_t* o, const StoredSpan& m, uint32_t cv, uint32_t key, unsigned lane)
+{
+    put_stored_head(o, m, cv, key, lane);
+    if (lane < 4) o[m.pay + lane] = (uint8_t)(lane < 2 ? 0x00 : 0xff) ^ key_byte(key, m.pay + lane);
+}
+
+// one wave per large message: its chunk blocks, each placed as deflate_plan.h says
 __global__ void __launch_bounds__(64)
 stitch_kernel(const uint32_t* __restrict__ in_len, uint32_t n, uint32_t all, const uint32_t* __restrict__ first,
               const uint8_t* __restrict__ temp, const uint32_t* __restrict__ bits, uint8_t* __restrict__ out,
@@ -1522,84 +1512,47 @@ stitch_kernel(const uint32_t* __restrict__ in_len, uint32_t n, uint32_t all, con
         uint8_t* o = out + out_off[i];
         const uint32_t cap = out_cap[i];
         const uint32_t key = mask_key ? mask_key[i] : 0u;
-        auto km = [&](uint32_t p) { return (uint8_t)(key >> (8 * (p & 3))); };
         uint32_t bit = 0;   // output bits so far
         uint32_t cv = 0;    // the partial byte at bit >> 3 (its low bit & 7 bits)
         bool overflow = false;
-        for (uint32_t c = 0; c < nk && !overflow; ++c) {
-            const uint32_t k = f + c;
-            const uint32_t w = bits[k];
-            if (w == 0xFFFFFFFFu) { overflow = true; break; }
+        for (uint32_t c = 0; c < nk; ++c) {
+            const uint32_t k = f + c, w = bits[k];
+            if (w == W_OVERFLOW) { overflow = true; break; }
             const uint8_t* t = temp + (size_t)k * SLOT;
-            const uint32_t L = w & 0x7FFFFFFFu;
-            if (c == 1 && (w & 0x80000000u)) {
-                // a stored chunk 1 gets the marker too, so every payload of two
-                // or more chunks carries one and a block-parallel inflater
-                // knows its Huffman blocks are all marked (pmd_inflate_bp.hip)
-                const uint32_t B = bit >> 3, P = (bit + 3 + 7) >> 3;
-                if (P + 4 + 1 > cap) { overflow = true; break; }
-                if (lane == 0) {
-                    o[B] = (uint8_t)cv ^ km(B);
-                    if (P - B == 2) o[B + 1] = km(B + 1);
-                }
-                if (lane < 4) o[P + lane] = (uint8_t)(lane < 2 ? 0x00 : 0xff) ^ km(P + lane);
-                bit = (P + 4) * 8;
-                cv = 0;
+            const bool stored = (w & W_STORED) != 0;
+            if (marker_before(c, stored)) {
+                const StoredSpan m = stored_span(bit, 4);
+                if (m.room > cap) { overflow = true; break; }
+                put_marker(o, m, cv, key, lane);
+                bit = m.next, cv = 0;
             }
-            const uint32_t B = bit >> 3, s = bit & 7;
-            if (w & 0x80000000u) {
-                // stored block: 000 at `bit`, pad to a byte, then LEN NLEN and the
-                // bytes (in the slot from byte 1: header + pad took byte 0)
-                const uint32_t P = (bit + 3 + 7) >> 3;
-                const uint32_t nbytes = L / 8 - 1;
-                if (P + nbytes + 1 > cap) { overflow = true; break; }
-                if (lane == 0) {
-                    o[B] = (uint8_t)cv ^ km(B);
-                    if (P - B == 2) o[B + 1] = km(B + 1);
-                }
-                for (uint32_t j = lane; j < nbytes; j += WAVE) o[P + j] = t[1 + j] ^ km(P + j);
-                bit = (P + nbytes) * 8;
-                cv = 0;
+            if (stored) {
+                // LEN NLEN and the bytes are in the slot from byte 1
+                const StoredSpan s = stored_span(bit, (w & ~W_STORED) / 8 - 1);
+                if (s.room > cap) { overflow = true; break; }
+                put_stored_head(o, s, cv, key, lane);
+                for (uint32_t j = lane; j < s.nbytes; j += WAVE) o[s.pay + j] = t[1 + j] ^ key_byte(key, s.pay + j);
+                bit = s.next, cv = 0;
             } else {
-                if (c) {
-                    // a marker before every Huffman-coded chunk but the first:
-                    // an empty stored block (000, pad, 00 00 FF FF), so the
-                    // block starts on a byte that a block-parallel inflater
-                    // finds by a byte search (pmd_inflate_bp.hip); ~5 bytes
-                    // per 4 KiB chunk
-                    const uint32_t P = (bit + 3 + 7) >> 3;
-                    if (P + 4 + 1 > cap) { overflow = true; break; }
-                    if (lane == 0) {
-                        o[B] = (uint8_t)cv ^ km(B);
-                        if (P - B == 2) o[B + 1] = km(B + 1);
-                    }
-                    if (lane < 4) o[P + lane] = (uint8_t)(lane < 2 ? 0x00 : 0xff) ^ km(P + lane);
-                    bit = (P + 4) * 8;
-                    cv = 0;
-                }
-                const uint32_t B = bit >> 3, s = bit & 7;
-                const uint32_t end = bit + L;
-                if (((end + 7) >> 3) + 1 > cap) { overflow = true; break; }
-                const uint32_t nb = (L + 7) >> 3;             // slot bytes
-                const uint32_t full = (end >> 3) - B;         // output bytes completed by this block
-                auto tb = [&](uint32_t j) -> uint32_t { return j < nb ? t[j] : 0u; };
+                const HuffSpan h = huff_span(bit, w);
+                if (h.room > cap) { overflow = true; break; }
+                auto tb = [&](uint32_t j) -> uint32_t { return j < h.slot_bytes ? t[j] : 0u; };
                 auto val = [&](uint32_t j) -> uint32_t {
-                    const uint32_t lo = s == 0 ? 0u : (j == 0 ? cv : tb(j - 1) >> (8 - s));
-                    return ((tb(j) << s) | lo) & 0xFFu;
+                    const uint32_t lo = h.shift == 0 ? 0u : (j == 0 ? cv : tb(j - 1) >> (8 - h.shift));
+                    return ((tb(j) << h.shift) | lo) & 0xFFu;
                 };
-                for (uint32_t j = lane; j < full; j += WAVE) o[B + j] = (uint8_t)val(j) ^ km(B + j);
-                cv = (end & 7) ? val(full) : 0u;
-                bit = end;
+                for (uint32_t j = lane; j < h.full; j += WAVE) o[h.at + j] = (uint8_t)val(j) ^ key_byte(key, h.at + j);
+                cv = (h.next & 7) ? val(h.full) : 0u;
+                bit = h.next;
             }
         }
         // Flush::sync's empty stored block header (000) + pad; 00 00 FF FF stripped
-        const uint32_t tbytes = (bit & 7) + 3 > 8 ? 2u : 1u;
-        const uint32_t olen = (bit >> 3) + tbytes;
+        const uint32_t at = bit >> 3, olen = tail_out_len(at, bit & 7);
         if (!overflow && olen > cap) overflow = true;
         if (lane == 0) {
             if (!overflow) {
-                o[bit >> 3] = (uint8_t)cv ^ km(bit >> 3);
-                if (tbytes == 2) o[(bit >> 3) + 1] = km((bit >> 3) + 1);
+                o[at] = (uint8_t)cv ^ key_byte(key, at);
+                if (olen - at == 2) o[at + 1] = key_byte(key, at + 1);
             }
             out_len[i] = overflow ? 0u : olen;
             if (out_bits) out_bits[i] = overflow ? 0u : bit;
@@ -1632,70 +1585,44 @@ int launch_single(const bpmd::Batch& b, const bpmd::dfl::Params& P, hipStream_t 
                        b.out_off, b.out_cap, b.out_len, b.status, P, qctr);
     return (int)hipGetLastError();
 }
-}  // namespace
 
-namespace {
-// tune: null, or deflate_stream::tune's (good_length, max_lazy, nice_length,
-// max_chain) (deflate_stream.ipp:307-317) replacing the level's table row;
-// the level still picks the parser, and the chain keeps the engine's caps
-// host_chunks >= 0: the caller knows the batch's chunk count (the per-stream
-// deflater, one message of known length: exact_chunks) or a bound on it (the
-// chained takeover send, n * ceil(L / 4096)), so nothing is read back.  The
-// host value lays out the workspace and caps the chunk kernel's grid; the
-// kernels take the count itself from d_total on the device, so any value at
-// least the count serves, except on the one-message path, whose setup kernel
-// writes the host value as the count.
-int deflate_impl(const bpmd::Batch& b, uint32_t* out_bits, const uint32_t* mask_key, const uint32_t* hist_len, int level,
-                 int window_bits, int strategy, hipStream_t stream, const int* tune = nullptr, int64_t host_chunks = -1,
-                 bool exact_chunks = true)
+// step 1.  tune: null, or deflate_stream::tune's (good_length, max_lazy,
+// nice_length, max_chain) (deflate_stream.ipp:307-317) replacing the level's
+// table row; the level still picks the parser
+bpmd::dfl::Params make_params(const bpmd::DeflateOpts& o)
 {
-    const auto& [in, in_off, in_len, n, out, out_off, out_cap, out_len, status] = b;
     bpmd::dfl::Params P;
-    P.L = lz::level_params(level);
+    P.L = lz::level_params(o.level);
     auto clamp16 = [](int v) { return (uint16_t)(v < 0 ? 0 : v > 65535 ? 65535 : v); };
-    if (tune) {
-        P.L.good = clamp16(tune[0]);
-        P.L.lazy = clamp16(tune[1]);
-        P.L.nice = clamp16(tune[2]);
-        P.L.chain = clamp16(tune[3]);
+    if (o.tune) {
+        P.L.good = clamp16(o.tune[0]), P.L.lazy = clamp16(o.tune[1]);
+        P.L.nice = clamp16(o.tune[2]), P.L.chain = clamp16(o.tune[3]);
     }
-    auto chain = [&](bool single) {
-        const unsigned cap = single ? (unsigned)BPMD_CHAIN_CAP : (unsigned)BPMD_CHAIN_CAP_MULTI;
-        return cap && P.L.chain > cap ? cap : (unsigned)P.L.chain;
-    };
-    P.strategy = strategy;
-    const unsigned wsize = 1u << window_bits;
-    P.max_dist = wsize - lz::LOOKAHEAD_MIN;
-    P.out_bits = out_bits;
-    P.mask_key = mask_key;
-    P.hist_len = hist_len;
-    using namespace bpmd::dfl;
-    const uint32_t all = hist_len ? 1u : 0u;   // context takeover: every message needs its history window
-    // how many chunk blocks the large messages make (one small read back: it
-    // sizes the workspace; the single-chunk kernel is enqueued right after it
-    // and runs meanwhile)
-    uint32_t* d_total = (uint32_t*)bpmd::scratch_block(stream, 256, bpmd::SCR_DEFLATE_COUNT);   // [0] chunk count, [32] chunk queue
-    if (!d_total) return (int)hipErrorOutOfMemory;
-    // one message with its chunk count known (a stream's write): one setup
-    // launch below instead of the memset, the count, the scan and the fill
-    const bool one = n == 1 && host_chunks >= 0 && exact_chunks;
+    P.strategy = o.strategy;
+    P.max_dist = (1u << o.window_bits) - lz::LOOKAHEAD_MIN;
+    P.out_bits = o.out_bits, P.mask_key = o.mask_key, P.hist_len = o.hist_len;
+    return P;
+}
+
+// step 2.  Counts the chunks on the device (d_total: [0] the count, [32] the
+// chunk queue), enqueues the single-chunk kernel (no takeover: !all) and gives
+// the host its total: the caller's, or the count read back while that kernel runs.
+int count_and_launch_single(const bpmd::Batch& b, const bpmd::dfl::Params& P, const bpmd::dfl::ChunkSource& src,
+                            uint32_t all, uint32_t* d_total, hipStream_t stream, uint32_t& total)
+{
     hipError_t he = hipSuccess;
-    if (!one) {
-        he = hipMemsetAsync(d_total, 0, 256, stream);
-        if (he != hipSuccess) return (int)he;
-        hipLaunchKernelGGL(count_chunks_kernel, dim3(n < 256 * 256 ? (n + 255) / 256 : 256), dim3(256), 0, stream, in_len,
-                           n, all, d_total);
+    if (!one_launch_setup(src, b.n)) {
+        if ((he = hipMemsetAsync(d_total, 0, 256, stream)) != hipSuccess) return (int)he;
+        hipLaunchKernelGGL(bpmd::dfl::count_chunks_kernel, dim3(b.n < 256 * 256 ? (b.n + 255) / 256 : 256), dim3(256), 0,
+                           stream, b.in_len, b.n, all, d_total);
     }
-    uint32_t total = 0;
-    P.chain = chain(true);
-    if (host_chunks >= 0) {
-        if (host_chunks > 0xFFFFFFFFll) return (int)hipErrorInvalidValue;
-        total = (uint32_t)host_chunks;   // the device count above is this number or less
-        const int e = all ? 0 : launch_single(b, P, stream);
-        if (e) return e;
-    } else {
-    // a pinned word of the stream (the caller holds its launch lock), so the
-    // copy is asynchronous and the event covers it
+    if (src.kind != bpmd::dfl::ChunkSource::READ_BACK) {
+        // EXACT: the device count, or what the setup launch writes; BOUND: that count or more
+        if (src.chunks > 0xFFFFFFFFull) return (int)hipErrorInvalidValue;
+        total = (uint32_t)src.chunks;
+        return all ? 0 : launch_single(b, P, stream);
+    }
+    // READ_BACK, through a pinned word of the stream: the copy is asynchronous, the event covers it
     uint32_t* h_total = (uint32_t*)bpmd::pinned_block(stream, 64, bpmd::PIN_DEFLATE_CHUNKS);
     if (!h_total) return (int)hipErrorOutOfMemory;
     hipEvent_t ev = nullptr;
@@ -1705,25 +1632,31 @@ int deflate_impl(const bpmd::Batch& b, uint32_t* out_bits, const uint32_t* mask_
         (void)hipEventDestroy(ev);
         return (int)he;
     }
-    int e = all ? 0 : launch_single(b, P, stream);
+    const int e = all ? 0 : launch_single(b, P, stream);
     he = hipEventSynchronize(ev);
     (void)hipEventDestroy(ev);
-    if (e) return e;
-    if (he != hipSuccess) return (int)he;
     total = *h_total;
-    }
-    const bool big = total > 0 || all;
-    if (!big) {
-        // the stitch also finishes zero-chunk messages only on the takeover path
-        return 0;
-    }
-    // workspace: first[n + 1] | items[total] | bits[total] | slots[total] | scan temp
-    // (total: the count, or the caller's bound on it)
-    // (round 5's single-write chunk kernel, which placed each chunk's block
-    // without the stitch's second write, measured slower -- a chunk's wave
-    // waits, holding its CU slot, for the chunk before it to finish encoding:
-    // C4 26.6 -> 23.8, C5 L1 27.6 -> 25.5 GiB/s, profiles/r05k_ab_single_write.log
-    // -- and was removed in round 6)
+    return e ? e : (int)he;
+}
+}  // namespace
+
+int bpmd::deflate(const Batch& b, const DeflateOpts& opts, hipStream_t stream)
+{
+    using namespace bpmd::dfl;
+    const auto& [in, in_off, in_len, n, out, out_off, out_cap, out_len, status] = b;
+    Params P = make_params(opts);
+    auto chain = [&](unsigned cap) { return cap && P.L.chain > cap ? cap : (unsigned)P.L.chain; };   // the engine's caps
+    const uint32_t all = opts.hist_len ? 1u : 0u;   // context takeover: every message needs its history window
+    const bool one = one_launch_setup(opts.chunks, n);
+    uint32_t* d_total = (uint32_t*)scratch_block(stream, 256, SCR_DEFLATE_COUNT);
+    if (!d_total) return (int)hipErrorOutOfMemory;
+    uint32_t total = 0;
+    P.chain = chain(BPMD_CHAIN_CAP);
+    if (const int e = count_and_launch_single(b, P, opts.chunks, all, d_total, stream, total)) return e;
+    // the stitch also finishes zero-chunk messages only on the takeover path
+    if (total == 0 && !all) return 0;
+    // step 3: the workspace
+    hipError_t he = hipSuccess;
     size_t cub_bytes = 0;
     hipcub::CountingInputIterator<uint32_t> idx(0);
     hipcub::TransformInputIterator<uint32_t, ChunkCountOp, hipcub::CountingInputIterator<uint32_t>> counts(
@@ -1732,74 +1665,40 @@ int deflate_impl(const bpmd::Batch& b, uint32_t* out_bits, const uint32_t* mask_
         (he = hipcub::DeviceScan::ExclusiveSum(nullptr, cub_bytes, counts, (uint32_t*)nullptr, n + 1, stream)) !=
             hipSuccess)
         return (int)he;
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t o_first = 0, o_items = up(o_first + 4ull * (n + 1)),
-                 o_bits = up(o_items + 4ull * total),
-                 o_slots = up(o_bits + 4ull * total),
-                 o_cub = up(o_slots + (size_t)SLOT * total), bytes = up(o_cub + cub_bytes);
-    uint8_t* ws = bpmd::scratch_block(stream, bytes, bpmd::SCR_DEFLATE_WS);
+    const Layout lay(n, total, cub_bytes);
+    uint8_t* ws = scratch_block(stream, lay.bytes, SCR_DEFLATE_WS);
     if (!ws) return (int)hipErrorOutOfMemory;
-    uint32_t* first = (uint32_t*)(ws + o_first);
-    uint32_t* items = (uint32_t*)(ws + o_items);
-    uint32_t* bits = (uint32_t*)(ws + o_bits);
-    uint8_t* slots = ws + o_slots;
+    uint32_t *first = (uint32_t*)(ws + lay.first), *items = (uint32_t*)(ws + lay.items);
+    uint32_t* bits = (uint32_t*)(ws + lay.bits);
+    uint8_t* slots = ws + lay.slots;
+    // step 4: first[] and items[], the chunks, the stitch
     if (one) {
         hipLaunchKernelGGL(one_msg_setup_kernel, dim3(1), dim3(64), 0, stream, d_total, first, items, total);
     } else {
-        if ((he = hipcub::DeviceScan::ExclusiveSum(ws + o_cub, cub_bytes, counts, first, n + 1, stream)) != hipSuccess)
+        if ((he = hipcub::DeviceScan::ExclusiveSum(ws + lay.scan, cub_bytes, counts, first, n + 1, stream)) != hipSuccess)
             return (int)he;
         const unsigned fgrid = n < 256 * 1024 ? (n + 255) / 256 : 1024;
         hipLaunchKernelGGL(fill_items_kernel, dim3(fgrid), dim3(256), 0, stream, in_len, n, all, first, items);
     }
-    const int cus = bpmd::cu_count();
-    P.chain = chain(false);
-    // the chunk kernel with the level's history (lz::chunk_hist: 2 KiB, or 4 KiB
-    // at the slow levels)
-    auto launch_chunks = [&](auto hist_tag) -> int {
+    const int cus = cu_count();
+    P.chain = chain(BPMD_CHAIN_CAP_MULTI);
+    // the chunk kernel with the level's history (lz::chunk_hist: 2 KiB, 4 KiB at the slow levels)
+    auto launch_chunks = [&](auto hist_tag) {
         constexpr int H = decltype(hist_tag)::value;
         const unsigned per_cu = (160u * 1024u) / (unsigned)sizeof(DefLds<H>);
         const unsigned grid = total < (uint32_t)cus * per_cu ? total : (unsigned)cus * per_cu;
         hipLaunchKernelGGL(deflate_chunks_kernel<H>, dim3(grid), dim3(64), 0, stream, b.in, b.in_off, b.in_len, items,
                            first, d_total, slots, bits, d_total + 32, P);
-        return 0;
     };
-    if (total) {
-        const int e = lz::chunk_hist(level) == lz::CHUNK_HIST_DEEP
-                          ? launch_chunks(std::integral_constant<int, (int)lz::CHUNK_HIST_DEEP>{})
-                          : launch_chunks(std::integral_constant<int, CHUNK_HIST>{});
-        if (e) return e;
-    }
+    if (total && lz::chunk_hist(opts.level) == lz::CHUNK_HIST_DEEP)
+        launch_chunks(std::integral_constant<int, (int)lz::CHUNK_HIST_DEEP>{});
+    else if (total)
+        launch_chunks(std::integral_constant<int, CHUNK_HIST>{});
     // the stitch: every chunked message (and the empty messages of a takeover batch)
-    {
-        const unsigned sgrid = n < (uint32_t)cus * 16 ? n : (unsigned)cus * 16;
-        hipLaunchKernelGGL(stitch_kernel, dim3(sgrid), dim3(64), 0, stream, in_len, n, all, first, slots, bits, out,
-                           out_off, out_cap, out_len, status, out_bits, mask_key);
-    }
+    const unsigned sgrid = n < (uint32_t)cus * 16 ? n : (unsigned)cus * 16;
+    hipLaunchKernelGGL(stitch_kernel, dim3(sgrid), dim3(64), 0, stream, in_len, n, all, first, slots, bits, out, out_off,
+                       out_cap, out_len, status, opts.out_bits, opts.mask_key);
     return (int)hipGetLastError();
-}
-}  // namespace
-
-int64_t bpmd::deflate_chunks(uint32_t n, bool hist) { return dfl::chunk_count(n, hist); }
-
-// the per-stream deflater's flush (pmd_stream.hip): exact bit lengths, and
-// the stream's earlier plaintext before the message as history (context
-// takeover), hist_len null for none
-int bpmd::deflate_bits_hist(const Batch& b, uint32_t* out_bits, const uint32_t* hist_len, int level, int window_bits,
-                            int strategy, const int* tune, hipStream_t stream, int64_t host_chunks)
-{
-    return deflate_impl(b, out_bits, nullptr, hist_len, level, window_bits, strategy, stream, tune, host_chunks);
-}
-
-int bpmd::deflate_keyed(const Batch& b, int level, int window_bits, int strategy, const uint32_t* mask_key,
-                        hipStream_t stream)
-{
-    return deflate_impl(b, nullptr, mask_key, nullptr, level, window_bits, strategy, stream);
-}
-
-int bpmd::deflate_takeover(const Batch& b, int level, int window_bits, int strategy, const uint32_t* hist_len,
-                           hipStream_t stream, int64_t chunk_bound)
-{
-    return deflate_impl(b, nullptr, nullptr, hist_len, level, window_bits, strategy, stream, nullptr, chunk_bound, false);
 }
 
 extern "C" int bpmd_diag_deflate_counters(unsigned long long* out, int reset)

@@ -14,6 +14,7 @@
 #include <mutex>
 
 #include "bp.h"
+#include "deflate_plan.h"
 
 struct bpmd_cfg;   // include/beast_pmd.h
 
@@ -83,13 +84,6 @@ uint8_t* scratch_block(hipStream_t s, size_t bytes, ScratchSlot which);
 void* pinned_block(hipStream_t s, size_t bytes, PinnedSlot which);
 std::mutex* stream_mutex(hipStream_t s);
 
-// bpmd_deflate_takeover_batch without its wait: chunk_bound is at least the
-// batch's chunk count (at most 2^32 - 1), so the count is not read back and
-// the call only enqueues.  Checks cfg and takes the stream's launch lock as
-// the public call does.
-int deflate_takeover_bounded(const bpmd_cfg* cfg, const Batch& b, const uint32_t* hist_len, uint64_t chunk_bound,
-                             hipStream_t stream);
-
 // ---- pmd_send.hip: the send side's scan and frame launch, shared by
 // bpmd_send_batch and bpmd_send_takeover_batch.  launch_size enqueues the
 // caller's size kernel, which fills sizes[n] (0 = not sent) and the status so
@@ -140,18 +134,20 @@ void bp_release(hipStream_t s);
 int bp_reserve(hipStream_t s, unsigned long long in_bytes, unsigned long long out_bytes, unsigned long long msgs);
 
 // ---- pmd_deflate.hip, pmd_deflate_exact.hip
-int deflate_keyed(const Batch& b, int level, int window_bits, int strategy, const uint32_t* mask_key,
-                  hipStream_t stream);
-// chunk_bound >= 0: at least the batch's chunk count (the sum of
-// deflate_chunks(len, true)); the chunk count is then not read back
-int deflate_takeover(const Batch& b, int level, int window_bits, int strategy, const uint32_t* hist_len,
-                     hipStream_t stream, int64_t chunk_bound = -1);
-// the chunk count of one message of n bytes, with a history window or not:
-// deflate_bits_hist's host_chunks is the sum over its batch (for one message
-// exactly that; for more, that or any larger value)
-int64_t deflate_chunks(uint32_t n, bool hist);
-int deflate_bits_hist(const Batch& b, uint32_t* out_bits, const uint32_t* hist_len, int level, int window_bits,
-                      int strategy, const int* tune, hipStream_t stream, int64_t host_chunks);
+// what a deflate call is given besides its batch (the arrays: per message, on the device)
+struct DeflateOpts {
+    int level = 6, window_bits = 15, strategy = 0;
+    const int* tune = nullptr;            // deflate_stream::tune's four values, replacing the level's
+    const uint32_t* mask_key = nullptr;   // per message; null: unmasked
+    const uint32_t* hist_len = nullptr;   // context takeover: bytes of history before each message
+    uint32_t* out_bits = nullptr;         // receives each payload's exact bit length
+    dfl::ChunkSource chunks;              // (deflate_plan.h) read back unless the caller knows
+};
+int deflate(const Batch& b, const DeflateOpts& opts, hipStream_t stream);
+// pmd_capi.hip: bpmd_deflate_takeover_batch without its wait.  opts carries the
+// history lengths and a BOUND on the chunk count, so the call only enqueues; the
+// rest comes from cfg, checked, under the stream's launch lock, as in the public call.
+int deflate_takeover_bounded(const bpmd_cfg* cfg, const Batch& b, const DeflateOpts& opts, hipStream_t stream);
 int deflate_exact(const Batch& b, int level, int window_bits, int mem_level, int strategy, const uint32_t* mask_key,
                   hipStream_t stream);
 

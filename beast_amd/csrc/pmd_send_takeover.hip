@@ -187,7 +187,7 @@ extern "C" int bpmd_send_takeover_batch(const bpmd_cfg* cfg, const uint8_t* d_in
     if (r) return r;
     if (slot_bytes <= 2u * stp::K || max_len == 0) return BPMD_R_INVALID_ARGUMENT;
     const uint32_t L = stp::room(max_len, slot_bytes, stp::K);
-    const uint64_t bound = stp::chunk_bound(n, L);
+    const uint64_t bound = dfl::chunk_bound(n, L);   // none reaches the deflater with more than L bytes
     if (bound > 0xFFFFFFFFull) return BPMD_R_INVALID_ARGUMENT;
     if (n == 0) return BPMD_R_OK;
     if (!d_in || !d_in_off || !d_in_len || !d_buf || !d_base || !d_pos || !d_z || !d_z_off || !d_z_cap || !d_z_len ||
@@ -206,7 +206,9 @@ extern "C" int bpmd_send_takeover_batch(const bpmd_cfg* cfg, const uint8_t* d_in
     if (hipGetLastError() != hipSuccess) return BPMD_R_HIP_ERROR;
     // not under this stream's launch lock: the deflater takes it itself
     const Batch b{d_buf, w.z_off, w.z_in_len, n, d_z, d_z_off, d_z_cap, d_z_len, d_status};
-    r = deflate_takeover_bounded(cfg, b, w.z_hist, bound, s);
+    DeflateOpts zo;
+    zo.hist_len = w.z_hist, zo.chunks = {dfl::ChunkSource::BOUND, bound};
+    r = deflate_takeover_bounded(cfg, b, zo, s);
     if (r) return r;
     const dim3 egrid((n + 255u) / 256u), eblock(256);
     const SendFrames a{d_in, d_in_off, d_in_len, n, masked, frag != 0, frame_max, d_op, d_z, d_z_off, d_z_len,

@@ -445,7 +445,7 @@ void deflate_group(Arena& A, std::vector<DeflateJob*>& jobs)
     }
     const size_t in_at = o;
     size_t ib = 0;
-    int64_t chunks = 0;
+    uint64_t chunks = 0;
     for (uint32_t i = 0; i < k; ++i) {
         const bpmd::DeflateStep& s = *jobs[i]->st;
         if (s.n + s.hist_len > 0xFFFFFFFFu || s.out_cap > 0xFFFFFFFFu) {
@@ -454,7 +454,7 @@ void deflate_group(Arena& A, std::vector<DeflateJob*>& jobs)
         }
         io[i] = ib;
         ib = up256(ib + s.hist_len + s.n);
-        chunks += bpmd::deflate_chunks((uint32_t)s.n, s.hist_len != 0);
+        chunks += bpmd::dfl::chunk_count((uint32_t)s.n, s.hist_len != 0);
     }
     const size_t total = in_at + ib + 16;
     if (!A.reserve(total)) return fail_all(jobs, A.hs);
@@ -474,11 +474,15 @@ void deflate_group(Arena& A, std::vector<DeflateJob*>& jobs)
     const bpmd::Batch b{d + in_at, (const uint64_t*)(d + m_in_off), (const uint32_t*)(d + m_in_len), k, d + out_at,
                         (const uint64_t*)(d + m_out_off), (const uint32_t*)(d + m_out_cap), (uint32_t*)(d + m_out_len),
                         (int32_t*)(d + m_status)};
+    // exact bit lengths, the stream's earlier plaintext as history, the chunk count known here
+    bpmd::DeflateOpts zo;
+    zo.level = s0.level, zo.window_bits = s0.wbits, zo.strategy = s0.strategy, zo.tune = s0.tune;
+    zo.hist_len = hist ? (const uint32_t*)(d + m_hist) : nullptr, zo.out_bits = (uint32_t*)(d + m_bits);
+    zo.chunks = {bpmd::dfl::ChunkSource::EXACT, chunks};
     const bool ok =
         hipMemcpyAsync(d, h, out_at, hipMemcpyHostToDevice, A.hs) == hipSuccess &&
         (ib == 0 || hipMemcpyAsync(d + in_at, h + in_at, ib, hipMemcpyHostToDevice, A.hs) == hipSuccess) &&
-        bpmd::deflate_bits_hist(b, (uint32_t*)(d + m_bits), hist ? (const uint32_t*)(d + m_hist) : nullptr, s0.level,
-                                s0.wbits, s0.strategy, s0.tune, A.hs, chunks) == 0 &&
+        bpmd::deflate(b, zo, A.hs) == 0 &&
         read_back(A, 0, out_at, in_at, oo, [&](size_t i, size_t& len, size_t& room) {
             len = ((const uint32_t*)(h + m_out_len))[i];
             room = jobs[i]->st->out_cap;

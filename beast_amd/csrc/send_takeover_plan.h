@@ -20,14 +20,17 @@
 #pragma once
 #include <stdint.h>
 
+#include "deflate_plan.h"
 #include "lz_core.h"
 #include "send_plan.h"
 
 namespace bpmd {
 namespace stp {
 
-constexpr uint32_t K = 4096;       // pmd.TakeoverDeflater.HIST
-constexpr uint32_t CHUNK = 4096;   // the deflater's chunk (pmd_deflate.hip)
+constexpr uint32_t K = 4096;   // pmd.TakeoverDeflater.HIST
+// the deflater's (deflate_plan.h): chunk_bound(n, L), the most chunks it sees over n entries of <= L bytes
+using dfl::CHUNK;
+using dfl::chunk_bound;
 static_assert(K >= lz::CHUNK_HIST_DEEP && K >= (uint32_t)BPMD_CHUNK_HIST,
               "the buffer keeps at least lz::chunk_hist(level) bytes at every level");
 
@@ -97,10 +100,6 @@ BPMD_SP_HD uint32_t advance(uint32_t new_pos, uint32_t len, bool enters, int32_t
 {
     return enters && final_status == 0 ? new_pos + len : new_pos;
 }
-
-// The most 4 KiB chunks the deflater can see over n entries: none reaches it
-// with more than L bytes.
-BPMD_SP_HD uint64_t chunk_bound(uint32_t n, uint32_t L) { return (uint64_t)n * (((uint64_t)L + CHUNK - 1) / CHUNK); }
 
 }  // namespace stp
 }  // namespace bpmd

@@ -181,6 +181,40 @@ def test_write_batch_masks_the_deflate_payloads():
         assert st == 0 and out == msgs[i]
 
 
+def test_write_batch_masks_stored_chunks_and_their_marker():
+    """Random bytes leave the chunk-parallel path through its stored exit: two
+    and three stored chunks, so a masked marker before a stored chunk 1, and
+    one message whose chunk 0 is Huffman-coded JSON with stored chunks 1 and 2
+    behind it.  The unmasked bytes equal deflate_batch's, those the host
+    model's, and they inflate through the oracle."""
+    from tests.model import model as M
+    pmd = _pmd()
+    rng = random.Random(23)
+    msgs = [rng.randbytes(n) for n in (4097, 8192, 9000, 12288)]
+    js, _, _ = synth.make_batch("json", [4096], seed=23)
+    msgs.append(bytes(js) + rng.randbytes(9000 - 4096))
+    assert [len(m) for m in msgs] == [4097, 8192, 9000, 12288, 9000]
+    keys = [0x01020304, 0xA1B2C3D4, 0xFF00FF01, 0x80000001, 0x7E5DC3B2]
+    src = pmd.Batch.from_host(msgs)
+    plain = pmd.deflate_batch(src, level=6)
+    masked = pmd.write_batch(src, key=keys, level=6)
+    assert masked.status.cpu().tolist() == plain.status.cpu().tolist() == [0] * 5
+    pl, ms = plain.out.to_host(), masked.out.to_host()
+    lens = [len(m) for m in msgs]
+    off = [sum(lens[:i]) for i in range(5)]
+    want = M.encode(np.frombuffer(b"".join(msgs), dtype=np.uint8), off, lens, level=6)
+    for i in range(5):
+        # the paths meant are the ones taken: a stored block holds its chunk's bytes verbatim (every chunk
+        # of the random messages; chunks 1 and 2 of the last), and the last message's first block is not stored
+        for c in range(1 if i == 4 else 0, -(-lens[i] // 4096)):
+            assert msgs[i][4096 * c:4096 * (c + 1)] in pl[i], (i, c)
+        assert (len(pl[i]) > lens[i]) == (i < 4) and (i < 4 or (pl[i][0] >> 1) & 3 != 0), i
+        assert O.mask(ms[i], keys[i]) == pl[i], i
+        assert pl[i] == want[i], i
+        st, out = O.pmd_inflate(pl[i], cap=lens[i])
+        assert st == 0 and out == msgs[i], i
+
+
 @pytest.mark.parametrize("frame_max", [125, 126, 4096, 65536, 1 << 20])
 def test_frame_batch_matches_oracle(frame_max):
     """bpmd_frame_batch's wire bytes equal the oracle's frame loop

@@ -268,7 +268,7 @@ def _capacity_sweep(data, in_off, in_len, hist, caps, want, bits, level=6):
           % ("plain" if hist is None else "takeover", L, bits % 8, first))
     assert accepted == [c for c in caps if c >= first], "statuses are not monotone in cap"
     assert first in (L, L + 1), (first, L)
-    # read from the kernels' checks: the stitch (every takeover message, every
+    # DESIGN.md 4.2b, the smallest accepted capacity: the stitch (every takeover message, every
     # message over one chunk) asks for the byte after a Huffman block's last
     # one, which the tail does not need when the block ends 1-5 bits into a
     # byte; the single-chunk kernel asks for the payload's bytes
