@@ -1869,7 +1869,7 @@ __global__ void __launch_bounds__(256) order_keys_kernel(const uint32_t* __restr
 {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i < n) {
-        key[i] = in_len[i] >> 6;
+        key[i] = in_len[i] >> LANE_ORDER_KEY_SHIFT;
         idx[i] = i;
     }
 }

@@ -126,6 +126,8 @@ int inflate_lane3(const Batch& b, uint32_t raw, const uint32_t* mask_key, const 
 int inflate_lane3_seg(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint32_t n_tasks,
                       const bp::SegTask* tasks, uint16_t* sym, bp::SegRes* res, uint32_t raw, uint32_t* qctr,
                       uint32_t grid_wgs, hipStream_t stream, const uint32_t* n_dev);
+// the order's keys are in_len >> LANE_ORDER_KEY_SHIFT, descending (exact deflate's queue relies on it: exact_plan.h)
+constexpr uint32_t LANE_ORDER_KEY_SHIFT = 6;
 const uint32_t* lane_order(const uint32_t* in_len, uint32_t n, hipStream_t stream, const uint32_t** keys_out);
 
 // ---- pmd_inflate_bp.hip: block-parallel decode of long payloads

@@ -30,7 +30,7 @@ _L = None
 def build():
     os.makedirs(BUILD, exist_ok=True)
     deps = [BACKEND, os.path.join(CPP, "zstream_shim.h"), __file__] + [
-        os.path.join(CSRC, f) for f in ("pmd_zstream.hip", "zstream.h", "huff_table.h", "inflate_reader.h")]
+        os.path.join(CSRC, f) for f in ("pmd_zstream.hip", "zstream.h", "huff_table.h", "inflate_reader.h", "status.h")]
     if os.path.exists(LIB) and os.path.getmtime(LIB) >= max(os.path.getmtime(d) for d in deps):
         return LIB
     cmd = [CXX, "-O1", "-g", *os.environ.get("ZS_HOST_FLAGS", "").split(), "-std=c++17", "-fPIC", "-shared",

@@ -78,6 +78,15 @@ def test_window_slides_and_long_messages(level):
     _check(_msgs(("json",), (1500, 4000), seed=3), level, 9)
 
 
+@pytest.mark.parametrize("mem,wbits", [(4, 15), (5, 12), (6, 15)])
+def test_tier_edges_and_queue_band(mem, wbits):
+    # one launch with both tier edges (4096 / 4097, 7930 / 7931), the lengths whose order key lies in the
+    # 64 bytes below the workspace tier (where its queue must not end yet) and workspace messages on either
+    # side of them; at memLevel 6 every message is the workspace tier's and the queue runs to its end
+    _check(_msgs(("json", "binary"), (4095, 4096, 4097, 7866, 7867, 7929, 7930, 7931, 7994, 9000, 20000),
+                 seed=7 * mem + wbits), 6, wbits, mem)
+
+
 def test_c3_sample_exact():
     lens = np.full(512, 4096, dtype=np.uint32)
     d, off, ln = synth.make_batch("json", lens, seed=0x5EED0003)
