@@ -88,7 +88,9 @@ std::mutex* stream_mutex(hipStream_t s);
 // bpmd_send_batch and bpmd_send_takeover_batch.  launch_size enqueues the
 // caller's size kernel, which fills sizes[n] (0 = not sent) and the status so
 // far; then the 64-bit exclusive sum into wire_off and send_frame_kernel.
-// Takes the stream's launch lock.
+// Takes the stream's launch lock.  first / fin: per entry, whether the entry's
+// first frame opens a message (opcode, RSV1) and its last frame ends one (FIN);
+// NULL = every entry is a whole message (bpmd_send_pieces_batch passes both).
 struct SendFrames {
     const uint8_t* in;
     const uint64_t* in_off;
@@ -109,6 +111,8 @@ struct SendFrames {
     const uint8_t* compressed;
     int32_t* status;
     uint64_t* total;
+    const uint8_t* first = nullptr;
+    const uint8_t* fin = nullptr;
 };
 int send_scan_frames(const SendFrames& a, const std::function<void(uint64_t* sizes)>& launch_size, hipStream_t s);
 

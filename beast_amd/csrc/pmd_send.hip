@@ -114,7 +114,8 @@ send_size_kernel(const uint32_t* __restrict__ in_len, const uint32_t* __restrict
 // closed form.  A size of 0 marks a message that is not sent (every frame has
 // at least 2 bytes); a message that does not fit [0, wire_cap) at its packed
 // offset, or whose size does not fit d_wire_len's 32 bits, is refused and none
-// of its bytes are written.
+// of its bytes are written.  first / fin (NULL = all 1): an entry that is one
+// piece of a message opens it only with first[m] and ends it only with fin[m].
 __global__ void __launch_bounds__(WAVE * WPB)
 send_frame_kernel(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_off,
                   const uint32_t* __restrict__ in_len, const uint8_t* __restrict__ z,
@@ -123,7 +124,8 @@ send_frame_kernel(const uint8_t* __restrict__ in, const uint64_t* __restrict__ i
                   const uint32_t* __restrict__ keys, const uint32_t* __restrict__ key_base, uint32_t frag,
                   uint32_t frame_max, uint32_t n, const uint64_t* __restrict__ sizes, uint8_t* __restrict__ wire,
                   uint64_t wire_cap, const uint64_t* __restrict__ wire_off, uint32_t* __restrict__ wire_len,
-                  int32_t* __restrict__ status, uint64_t* __restrict__ total)
+                  int32_t* __restrict__ status, uint64_t* __restrict__ total, const uint8_t* __restrict__ first,
+                  const uint8_t* __restrict__ fin)
 {
     const unsigned lane = threadIdx.x & (WAVE - 1);
     const bool masked = keys != nullptr;
@@ -141,12 +143,13 @@ send_frame_kernel(const uint8_t* __restrict__ in, const uint64_t* __restrict__ i
         const sp::Split s = sp::split(c ? z_len[m] : in_len[m], frame_max, c, frag != 0);
         const uint32_t o = op ? op[m] : (uint32_t)sp::OP_BINARY;
         const uint32_t kb = masked ? key_base[m] : 0u;
+        const bool opens = first ? first[m] != 0 : true, ends = fin ? fin[m] != 0 : true;
         uint8_t* dst = wire + off;
         for (uint64_t f = 0; f < s.frames; ++f) {
             const uint32_t len = (uint32_t)sp::frame_len(s, f);
             const uint32_t key = masked ? keys[kb + f] : 0u;
             uint64_t h0, h1;
-            const uint32_t hl = sp::header(len, f == 0, f + 1 == s.frames, c, o, masked, key, h0, h1);
+            const uint32_t hl = sp::header(len, f == 0 && opens, f + 1 == s.frames && ends, c, o, masked, key, h0, h1);
             uint8_t* p = dst + sp::frame_off(s, masked, f);
             if (lane < hl) p[lane] = sp::header_byte(h0, h1, lane);
             copy_xor(p + hl, src + sp::frame_src(s, f), len, key, lane);
@@ -258,7 +261,8 @@ int bpmd::send_scan_frames(const SendFrames& a, const std::function<void(uint64_
         return BPMD_R_HIP_ERROR;
     hipLaunchKernelGGL(send::send_frame_kernel, dim3(wave_grid(n)), dim3(send::WAVE * send::WPB), 0, s, a.in, a.in_off,
                        a.in_len, a.z, a.z_off, a.z_len, a.op, a.compressed, a.keys, a.key_base, a.frag ? 1u : 0u,
-                       a.frame_max, n, sizes, a.wire, a.wire_cap, a.wire_off, a.wire_len, a.status, a.total);
+                       a.frame_max, n, sizes, a.wire, a.wire_cap, a.wire_off, a.wire_len, a.status, a.total, a.first,
+                       a.fin);
     return hipGetLastError() != hipSuccess ? BPMD_R_HIP_ERROR : BPMD_R_OK;
 }
 

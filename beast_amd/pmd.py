@@ -1260,6 +1260,130 @@ class TakeoverSender:
                     Result(Batch(self.z, self.z_off, z_len), self.z_cap, status), self.key_base)
 
 
+WR_STATE_BYTES = 4   # sizeof(bpmd_wr_state)
+
+
+def wr_state(n: int, device="cuda") -> torch.Tensor:
+    """n zeroed bpmd_wr_state records (uint8 [n, 4]: wr_cont, wr_compress,
+    wr_op, reserved): no message open on any connection."""
+    return torch.zeros((n, WR_STATE_BYTES), dtype=torch.uint8, device=device)
+
+
+def _send_pc_lib():
+    """_send_tk_lib() with bpmd_send_pieces_batch's prototypes, bound on first use"""
+    L = _send_tk_lib()
+    if not getattr(L, "_send_pc_ready", False):
+        vp, u32, u64, ci = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int
+        L.bpmd_send_piece_frame_bound.argtypes = [u64, u32, ci, ci, ci]
+        L.bpmd_send_piece_frame_bound.restype = u64
+        L.bpmd_send_piece_wire_bound.argtypes = [u64, u32, ci, ci, ci, ci]
+        L.bpmd_send_piece_wire_bound.restype = u64
+        L.bpmd_send_pieces_work_bytes.argtypes = [u32]
+        L.bpmd_send_pieces_work_bytes.restype = ctypes.c_size_t
+        L.bpmd_send_pieces_batch.argtypes = ([ctypes.POINTER(_Cfg), vp, vp, vp, u32, ci, u64, ci, u32, u32] + [vp] * 7
+                                             + [u32] + [vp] * 8 + [u64] + [vp] * 7)
+        L.bpmd_send_pieces_batch.restype = ci
+        L._send_pc_ready = True
+    return L
+
+
+def send_piece_bounds(n: int, frame_max: int = 4096, masked: bool = False, may_compress: bool = True,
+                      frag: bool = True, fin: bool = False):
+    """(bpmd_send_piece_frame_bound, bpmd_send_piece_wire_bound): the most
+    frames (keys, in client role) and wire bytes one piece of n input bytes can
+    take; a non-final piece (`fin` false) counts its 00 00 FF FF."""
+    L = _send_pc_lib()
+    return (int(L.bpmd_send_piece_frame_bound(n, frame_max, int(may_compress), int(frag), int(fin))),
+            int(L.bpmd_send_piece_wire_bound(n, frame_max, int(masked), int(may_compress), int(frag), int(fin))))
+
+
+class PieceSender:
+    """bpmd_send_pieces_batch over n_conn connections: TakeoverSender for
+    messages that arrive in pieces, as an application calls Beast's
+    write_some(fin, buffers).  Entry i of every call is connection i's next
+    piece (op 0: nothing to send); the first piece of a message decides
+    whether the message is compressed, from its own length, and carries the
+    opcode; `fin` marks a message's last piece.  `state` (wr_state) and `pos`
+    stay on the device, so connections at any point of their messages share a
+    call.  `no_takeover`: per connection (or one value), whether
+    no_context_takeover was negotiated -- its history is reset after every
+    compressed message -- None = none.  `max_piece` bounds a piece, not a
+    message: keys (client role: `key_stride` per connection, frame f of
+    connection i's piece takes keys[i * key_stride + f]) and the default wire
+    (`wire_bound` bytes per connection) are sized from it with
+    send_piece_bounds.  A connection whose piece came back with a non-zero
+    status has not moved: send the piece again (a shorter one after
+    WS_MESSAGE_TOO_BIG), the others idle.  A Sent's tensors of one call are
+    valid until the next."""
+
+    HIST = 4096
+
+    def __init__(self, n_conn: int, role: int, level: int = 6, window_bits: int = 15, mem_level: int = 4,
+                 max_piece: int = 1 << 16, threshold: int = 0, frag: bool = True, frame_max: int = 4096,
+                 no_takeover=None, device="cuda"):
+        L = _send_pc_lib()
+        self.n, self.role, self.max_piece = n_conn, role, max_piece
+        self.threshold, self.frag, self.frame_max = threshold, frag, frame_max
+        self.cfg = _Cfg(level, window_bits, mem_level, 0, 0)
+        self.slot = (2 * self.HIST + max_piece + 15) // 16 * 16
+        self.buf = torch.zeros(n_conn * self.slot + 16, dtype=torch.uint8, device=device)
+        self.base = torch.arange(n_conn, dtype=torch.int64, device=device) * self.slot
+        self.pos = torch.zeros(n_conn, dtype=torch.int32, device=device)
+        self.state = wr_state(n_conn, device)
+        self.no_takeover = _u8(no_takeover, n_conn, device)
+        masked = role == ROLE_CLIENT
+        self.key_stride, self.wire_bound = send_piece_bounds(max_piece, frame_max, masked, True, frag, False)
+        self.key_base = (torch.arange(n_conn, dtype=torch.int32, device=device) * self.key_stride) if masked else None
+        zc = (upper_bound(max_piece) + 4 + 15) // 16 * 16
+        self.z = torch.empty(n_conn * zc + 16, dtype=torch.uint8, device=device)
+        self.z_off = torch.arange(n_conn, dtype=torch.int64, device=device) * zc
+        self.z_cap = torch.full((n_conn,), zc, dtype=torch.int32, device=device)
+        self.work = torch.empty(max(int(L.bpmd_send_pieces_work_bytes(n_conn)), 1), dtype=torch.uint8, device=device)
+
+    def send(self, src: Batch, op, fin, opt=None, keys=None, wire: torch.Tensor | None = None, stream=None) -> Sent:
+        """One call over src (entry i: connection i's piece).  `op`: 0 idle,
+        1 text, 2 binary, per connection or one value (a continuation piece's
+        only has to be 1 or 2); `fin`: the piece is its message's last, per
+        connection or one value (None = all); `opt`: wr_compress_opt, looked at
+        on a message's first piece (None = on).  Everything is enqueued on
+        `stream`; with `wire` given the call reads nothing back, without it
+        the call also checks the lengths against max_piece."""
+        L = _send_pc_lib()
+        dev = self.buf.device
+        n = src.n
+        if n != self.n:
+            raise BpmdError("PieceSender.send: one entry per connection")
+        masked = self.role == ROLE_CLIENT
+        kt = None
+        if masked:
+            if keys is None:
+                raise BpmdError("PieceSender.send: client role needs keys")
+            kt = _keys(keys, int(keys.numel()) if isinstance(keys, torch.Tensor) else len(keys), dev)
+            if kt.numel() < n * self.key_stride:
+                raise BpmdError("PieceSender.send: keys must hold key_stride keys per connection")
+        with _on(stream):
+            op_t, opt_t, fin_t = _u8(op, n, dev), _u8(opt, n, dev), _u8(fin, n, dev)
+            if wire is None:
+                if n and int(src.len.max().item()) > self.max_piece:
+                    raise BpmdError("piece exceeds max_piece")
+                wire = torch.empty(n * self.wire_bound + 16, dtype=torch.uint8, device=dev)
+            z_len = torch.zeros(n, dtype=torch.int32, device=dev)
+            w_off = torch.zeros(n, dtype=torch.int64, device=dev)
+            w_len = torch.zeros(n, dtype=torch.int32, device=dev)
+            comp = torch.zeros(n, dtype=torch.uint8, device=dev)
+            status = torch.zeros(n, dtype=torch.int32, device=dev)
+            total = torch.zeros(1, dtype=torch.int64, device=dev)
+        _check(L.bpmd_send_pieces_batch(
+            ctypes.byref(self.cfg), _ptr(src.data), _ptr(src.off), _ptr(src.len), n, self.role, self.threshold,
+            1 if self.frag else 0, self.frame_max, self.max_piece, _optr(op_t), _optr(opt_t), _optr(fin_t),
+            _optr(self.no_takeover), _ptr(self.state), _ptr(self.buf), _ptr(self.base), self.slot, _ptr(self.pos),
+            _ptr(self.z), _ptr(self.z_off), _ptr(self.z_cap), _ptr(z_len), _optr(kt), _optr(self.key_base), _ptr(wire),
+            wire.numel(), _ptr(w_off), _ptr(w_len), _ptr(comp), _ptr(status), _ptr(total), _ptr(self.work),
+            _stream_handle(stream)), "bpmd_send_pieces_batch")
+        return Sent(Batch(wire, w_off, w_len), status, comp, total,
+                    Result(Batch(self.z, self.z_off, z_len), self.z_cap, status), self.key_base)
+
+
 @dataclass
 class Controls:
     wire: Batch            # one frame per entry at 144 * i; len 0 = refused

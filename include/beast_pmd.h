@@ -499,8 +499,8 @@ int bpmd_receive_batch(const bpmd_cfg* cfg, int role, int pmd_on, uint64_t msg_m
  * chunk count, above) is inherited when such a message is compressed.
  * Until the call returns, d_wire_len holds the deflater's input lengths.
  * Context-takeover sends have their own chained call,
- * bpmd_send_takeover_batch (below).  Deliberately out of scope: a message
- * that arrives in several write_some pieces.
+ * bpmd_send_takeover_batch (below), and a message that arrives in several
+ * write_some pieces goes through bpmd_send_pieces_batch (below).
  * n == 0 is a no-op; BPMD_R_INVALID_ARGUMENT for frame_max == 0, a role that
  * is neither value, client role without d_keys / d_key_base, a NULL required
  * pointer, or (pmd_on) a cfg bpmd_deflate_batch refuses; BPMD_R_NO_DEVICE
@@ -785,6 +785,101 @@ int bpmd_send_takeover_batch(const bpmd_cfg* cfg, const uint8_t* d_in, const uin
                              const uint32_t* d_keys, const uint32_t* d_key_base, uint8_t* d_wire, uint64_t wire_cap,
                              uint64_t* d_wire_off, uint32_t* d_wire_len, uint8_t* d_compressed, int32_t* d_status,
                              uint64_t* d_total, void* d_work, void* stream);
+
+/* A message in pieces: bpmd_send_takeover_batch with Beast's
+ * write_some(fin, buffers) state (websocket/impl/write.hpp:625-831) kept per
+ * connection, so an application streams a message as write_some(false, ...)
+ * ... write_some(true, ...), one piece per connection per call, and with a
+ * per-connection no_context_takeover flag, so connections that negotiated it
+ * and connections that did not share one call.  bpmd_rd_state's counterpart.
+ *
+ * d_state[i] (in/out, required) is connection i's wr_cont_, wr_compress_ and
+ * opcode; all zero = no message open, which is how a connection starts.
+ * d_fin[i] != 0 marks a message's final piece (NULL = every piece is final:
+ * whole messages).  d_no_takeover[i] != 0 marks a connection that negotiated
+ * no_context_takeover for this direction (NULL = none).  Everything not named
+ * here means what it means in bpmd_send_takeover_batch, with "message" read
+ * as "piece": d_in, d_in_off, d_in_len, role, frag, frame_max, the buffers
+ * d_buf / d_base / slot_bytes / d_pos with K and L, the staging slots, the
+ * keys d_keys[d_key_base[i] + f] with f counted from 0 in every piece, the
+ * packed wire, d_work and the guarantees about d_buf and d_wire.
+ *   - A piece with d_state[i].wr_cont == 0 begins a message: begin_msg
+ *     decides from this piece alone, compressed iff d_op[i] is 1 or 2,
+ *     d_opt[i] and d_in_len[i] >= threshold (Beast passes this write_some's
+ *     buffer_bytes, write.hpp:640-652; stream_impl.hpp:225-252), and its
+ *     first frame carries d_op[i], with RSV1 iff compressed.  A piece with
+ *     wr_cont != 0 continues the open message under the stored decision and
+ *     opcode: d_opt[i] is ignored, d_op[i] must be 1 or 2 (0 = idle, as ever)
+ *     and is otherwise ignored, and all its frames are continuation frames.
+ *     FIN is set on the piece's last frame iff d_fin[i].  A piece always
+ *     yields at least one frame, an empty one for an empty uncompressed piece.
+ *     d_compressed[i] is the message's decision on every piece (0 for an idle
+ *     entry or a bad opcode).
+ *   - A piece of a compressed message enters the connection's buffer and is
+ *     deflated as a message is in bpmd_send_takeover_batch, with the earlier
+ *     pieces as its history like any earlier plaintext.  The deflater's
+ *     payload ends with an empty stored block whose 00 00 FF FF is stripped,
+ *     and none of its blocks has BFINAL set; the final piece goes out like
+ *     that.  A non-final piece gets the four bytes back: they are written at
+ *     d_z + d_z_off[i] + d_z_len[i] and d_z_len[i] grows by 4, so the next
+ *     piece's blocks follow at a byte boundary (RFC 7692 7.2.1) and a
+ *     message's piece payloads concatenated are one valid permessage-deflate
+ *     payload.  Size a staging slot bpmd_deflate_upper_bound(len) + 4.  If the
+ *     four bytes do not fit d_z_cap[i] the piece gets BPMD_NEED_BUFFERS and
+ *     none of them is written.  (Beast sends a non-final piece with
+ *     Flush::none and may emit nothing, write.hpp:669-678; the payload bytes
+ *     differ, the inflated message does not.)  L bounds a piece, not a
+ *     message: a compressed piece longer than L gets BPMD_WS_MESSAGE_TOO_BIG
+ *     and can be sent again as shorter pieces.
+ *   - A piece of an uncompressed message is framed straight from d_in (frag
+ *     as in bpmd_send_batch) and never enters the history.
+ *   - After a piece with final status 0: d_pos[i] has advanced by d_in_len[i]
+ *     if the piece was deflated; wr_cont = !d_fin[i], wr_compress and the
+ *     opcode are the message's; and if the piece was final, the message
+ *     compressed and d_no_takeover[i] set, d_pos[i] = 0: the next message
+ *     starts without history (do_context_takeover_write,
+ *     impl_base.hpp:156-166).
+ *   - d_status[i], by precedence: BPMD_WS_BAD_OPCODE (d_op[i] not 0, 1 or 2),
+ *     BPMD_WS_MESSAGE_TOO_BIG, BPMD_NEED_BUFFERS (the deflater's, or the
+ *     marker's), BPMD_WS_BUFFER_OVERFLOW for the wire, 0.  An entry with any
+ *     non-zero status, like an idle one, has d_state[i] and the connection's
+ *     history exactly as they were, and d_pos[i] too but for a slide, which
+ *     keeps the history's bytes (d_pos[i] = K): the caller sends the same
+ *     piece again with more room, or a shorter one after
+ *     BPMD_WS_MESSAGE_TOO_BIG.
+ * Besides bpmd_send_takeover_batch's bytes the only staging bytes written are
+ * the four marker bytes of a non-final compressed piece whose slot has room.
+ * d_state[i] and d_pos[i] are written only when their value changes.
+ *
+ * bpmd_send_piece_frame_bound / bpmd_send_piece_wire_bound (host only) are
+ * bpmd_send_frame_bound / bpmd_send_wire_bound for a piece of `len` input
+ * bytes: with fin == 0 they count the marker.  may_compress: the message may
+ * be compressed (for a continuation piece, the stored decision if known).
+ *
+ * d_work: bpmd_send_pieces_work_bytes(n) (host only) bytes.  Everything is
+ * enqueued on `stream` and nothing is read back, as in
+ * bpmd_send_takeover_batch.  n == 0 is a no-op; BPMD_R_INVALID_ARGUMENT as
+ * there, and for a NULL d_state (d_fin and d_no_takeover may be NULL).
+ * Out of scope: BPMD_F_EXACT, and more than one piece of a connection in one
+ * call. */
+typedef struct bpmd_wr_state {
+    uint8_t wr_cont;       /* a message is open */
+    uint8_t wr_compress;   /* its begin_msg decision */
+    uint8_t wr_op;         /* its opcode */
+    uint8_t reserved;
+} bpmd_wr_state;           /* zero = no message open */
+uint64_t bpmd_send_piece_frame_bound(uint64_t len, uint32_t frame_max, int may_compress, int frag, int fin);
+uint64_t bpmd_send_piece_wire_bound(uint64_t len, uint32_t frame_max, int masked, int may_compress, int frag, int fin);
+size_t bpmd_send_pieces_work_bytes(uint32_t n);
+int bpmd_send_pieces_batch(const bpmd_cfg* cfg, const uint8_t* d_in, const uint64_t* d_in_off,
+                           const uint32_t* d_in_len, uint32_t n, int role, uint64_t threshold, int frag,
+                           uint32_t frame_max, uint32_t max_len, const uint8_t* d_op, const uint8_t* d_opt,
+                           const uint8_t* d_fin, const uint8_t* d_no_takeover, bpmd_wr_state* d_state, uint8_t* d_buf,
+                           const uint64_t* d_base, uint32_t slot_bytes, uint32_t* d_pos, uint8_t* d_z,
+                           const uint64_t* d_z_off, const uint32_t* d_z_cap, uint32_t* d_z_len, const uint32_t* d_keys,
+                           const uint32_t* d_key_base, uint8_t* d_wire, uint64_t wire_cap, uint64_t* d_wire_off,
+                           uint32_t* d_wire_len, uint8_t* d_compressed, int32_t* d_status, uint64_t* d_total,
+                           void* d_work, void* stream);
 
 /* ---------------------------------------------------------------------
  * Per-stream API behind the C++ compatibility facade
