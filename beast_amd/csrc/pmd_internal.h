@@ -186,6 +186,8 @@ void bpmd_internal_scratch_release(hipStream_t s);
 int bpmd_internal_zstream_write(void* st, const uint8_t* in, uint64_t n_in, uint8_t* out, uint64_t cap, int flush,
                                 void* res, hipStream_t stream);
 int bpmd_internal_zstream_write_batch(const void* calls, uint32_t n, hipStream_t stream);
+// the same launch over records written on the device; a record whose st is NULL runs nothing
+int bpmd_internal_zstream_write_sel(const void* calls, uint32_t n, hipStream_t stream);
 const uint32_t* bpmd_internal_lane_long_split(const uint32_t* in_len, const uint32_t* keys, uint32_t n, uint32_t lanes,
                                               uint32_t min_thr, uint32_t share_pct, hipStream_t stream);
 }

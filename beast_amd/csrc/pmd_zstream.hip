@@ -1268,6 +1268,18 @@ zstream_write_batch_kernel(const ZCall* __restrict__ calls, int par)
     const ZCall c = calls[blockIdx.x];
     zstream_run(L, (State*)c.st, c.in, c.n_in, c.out, c.cap, c.flush, (Result*)c.res, par & 9);
 }
+
+// the chained piece receive's launch (pmd_receive_pieces.hip): the batch
+// kernel over call records written on the device, where a record without a
+// state (st == NULL) is an entry with nothing to inflate
+__global__ void __launch_bounds__(WAVE)
+zstream_write_sel_kernel(const ZCall* __restrict__ calls, int par)
+{
+    __shared__ Lds L;
+    const ZCall c = calls[blockIdx.x];
+    if (c.st == nullptr) return;   // workgroup-uniform
+    zstream_run(L, (State*)c.st, c.in, c.n_in, c.out, c.cap, c.flush, (Result*)c.res, par & 9);
+}
 #endif
 
 }  // namespace zst
@@ -1325,6 +1337,16 @@ extern "C" int bpmd_internal_zstream_write_batch(const void* calls, uint32_t n, 
     if (n == 0) return 0;
     const int par = zstream_par();
     hipLaunchKernelGGL(zstream_write_batch_kernel, dim3(n), dim3(bpmd::WAVE), 0, stream, (const ZCall*)calls, par);
+    return (int)hipGetLastError();
+}
+
+// the same over call records the device wrote: a record with st == NULL runs nothing
+extern "C" int bpmd_internal_zstream_write_sel(const void* calls, uint32_t n, hipStream_t stream)
+{
+    using namespace bpmd::zst;
+    if (n == 0) return 0;
+    const int par = zstream_par();
+    hipLaunchKernelGGL(zstream_write_sel_kernel, dim3(n), dim3(bpmd::WAVE), 0, stream, (const ZCall*)calls, par);
     return (int)hipGetLastError();
 }
 

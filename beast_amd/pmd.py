@@ -1384,6 +1384,122 @@ class PieceSender:
                     Result(Batch(self.z, self.z_off, z_len), self.z_cap, status), self.key_base)
 
 
+RD_PIECE_STATE_BYTES = 32   # sizeof(bpmd_rd_piece_state)
+
+
+def rd_piece_state(n: int, device="cuda") -> torch.Tensor:
+    """n zeroed bpmd_rd_piece_state records (uint8 [n, 32]: rd_size and
+    rd_remain little-endian in bytes 0-7 and 8-15, rd_key in 16-19, then
+    rd_cont, rd_op, rd_deflated, rd_fin, utf8_n, utf8_b[3]): every connection
+    between messages."""
+    return torch.zeros((n, RD_PIECE_STATE_BYTES), dtype=torch.uint8, device=device)
+
+
+def _recv_pc_lib():
+    """lib() with bpmd_receive_pieces_batch's prototypes, bound on first use"""
+    L = lib()
+    if not getattr(L, "_recv_pc_ready", False):
+        vp, u32, ci = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int
+        L.bpmd_receive_pieces_zstate_bytes.argtypes = []
+        L.bpmd_receive_pieces_zstate_bytes.restype = ctypes.c_size_t
+        L.bpmd_receive_pieces_work_bytes.argtypes = [u32]
+        L.bpmd_receive_pieces_work_bytes.restype = ctypes.c_size_t
+        L.bpmd_receive_pieces_batch.argtypes = [ctypes.POINTER(_Cfg), ci, ci, ctypes.c_uint64, vp, vp, vp, u32] + \
+            [vp] * 20
+        L.bpmd_receive_pieces_batch.restype = ci
+        L._recv_pc_ready = True
+    return L
+
+
+@dataclass
+class RecvPieces(Recv):
+    """A Recv whose entries are pieces: frames.out.len is the gathered length
+    of this call's piece, msg.len the bytes delivered, and EV_MESSAGE marks a
+    message's last piece."""
+
+    def to_host(self):
+        """Per entry the bytes this call delivered (from the slot
+        frames.compressed names), b"" when there are none."""
+        comp, ln = self.frames.compressed.cpu().tolist(), self.msg.len.cpu().tolist()
+        # each buffer and offset array crosses to the host once
+        host = [(b.data.cpu().numpy(), b.off.cpu().tolist()) for b in (self.frames.out, self.msg)]
+        out = []
+        for i, k in enumerate(ln):
+            data, off = host[1 if comp[i] else 0]
+            out.append(data[off[i]:off[i] + k].tobytes())
+        return out
+
+
+class PieceReceiver:
+    """bpmd_receive_pieces_batch over n_conn connections: PieceSender's
+    counterpart, Beast's read_some with its state on the device.  Entry i of
+    every call is connection i's unconsumed wire bytes (length 0: idle); a call
+    delivers one piece per connection -- what has arrived of the current
+    message, inflated by the connection's own state machine, checked as UTF-8
+    with the cut code point carried -- and EV_MESSAGE marks a message's last.
+    The caller drops `consumed` bytes of each connection and calls again with
+    the rest (after EV_NEED_MORE with nothing consumed: once more has come).
+    The receiver owns `state` (rd_piece_state), the inflater states `zstate`
+    and the workspace; slots are sized per call, and a RecvPieces' tensors are
+    valid until the next call.  A connection that reported an error is dropped
+    by the caller: its states are unspecified."""
+
+    def __init__(self, n_conn: int, role: int, window_bits: int = 15, pmd_on: bool = True, msg_max: int = 16 << 20,
+                 device="cuda"):
+        L = _recv_pc_lib()
+        self.n, self.role, self.wbits, self.pmd_on, self.msg_max = n_conn, role, window_bits, pmd_on, msg_max
+        self.state = rd_piece_state(n_conn, device)
+        self.zstate = self.work = None
+        if pmd_on:
+            self.zstate = torch.zeros(max(n_conn * int(L.bpmd_receive_pieces_zstate_bytes()), 16), dtype=torch.uint8,
+                                      device=device)
+            self.work = torch.empty(max(int(L.bpmd_receive_pieces_work_bytes(n_conn)), 1), dtype=torch.uint8,
+                                    device=device)
+
+    def recv(self, wire: Batch, out_cap, msg_cap, stream=None, out: torch.Tensor | None = None,
+             out_off: torch.Tensor | None = None, msg: torch.Tensor | None = None,
+             msg_off: torch.Tensor | None = None) -> RecvPieces:
+        """One call over wire.  `out_cap` (>= 8): bytes of every gathered slot,
+        of which a call fills at most out_cap - 4; `msg_cap`: the room of every
+        inflated piece.  Each is one int, or an int32 tensor with the caller's
+        buffer and offsets (`out` must stay readable for 15 bytes past every
+        slot).  Everything is enqueued on `stream`; the call never waits."""
+        L = _recv_pc_lib()
+        dev = self.state.device
+        n = wire.n
+        if n != self.n:
+            raise BpmdError("PieceReceiver.recv: one entry per connection")
+        if isinstance(out_cap, int) and out_cap < 8:
+            raise BpmdError("PieceReceiver.recv: out_cap below 8")
+        with _on(stream):
+            cap, out, out_off = _host_slots("out", n, dev, out_cap, out, out_off)
+            out_len = torch.empty(n, dtype=torch.int32, device=dev)
+            u8 = lambda *shape: torch.empty(shape, dtype=torch.uint8, device=dev)  # noqa: E731
+            op, comp, event, ctl_len, ctl = u8(n), u8(n), u8(n), u8(n), u8(n, CTL_SLOT)
+            status = torch.empty(n, dtype=torch.int32, device=dev)
+            consumed = torch.empty(n, dtype=torch.int32, device=dev)
+            code = torch.empty(n, dtype=torch.int16, device=dev)
+            msg_len = torch.empty(n, dtype=torch.int32, device=dev)
+            mcap = None
+            if self.pmd_on:
+                mcap, msg, msg_off = _host_slots("msg", n, dev, msg_cap, msg, msg_off)
+            else:
+                msg, msg_off = u8(0), torch.zeros(n, dtype=torch.int64, device=dev)
+        on = self.pmd_on
+        cfg = _Cfg(0, self.wbits, 8, 0, 0)
+        _check(L.bpmd_receive_pieces_batch(
+            ctypes.byref(cfg) if on else None, self.role, 1 if on else 0, self.msg_max, _ptr(wire.data),
+            _ptr(wire.off), _ptr(wire.len), n, _ptr(self.state), _optr(self.zstate), _ptr(out), _ptr(out_off),
+            _ptr(cap), _ptr(out_len), _ptr(op), _ptr(comp), _ptr(event), _ptr(status), _ptr(consumed), _ptr(ctl),
+            _ptr(ctl_len), _ptr(code), _ptr(msg) if on else None, _ptr(msg_off) if on else None, _optr(mcap),
+            _ptr(msg_len), _optr(self.work), _stream_handle(stream)), "bpmd_receive_pieces_batch")
+        with _on(stream):
+            code = code.to(torch.int32) & 0xFFFF
+        frames = Unframed(Batch(out, out_off, out_len), cap, op, comp, event, status, consumed, ctl, ctl_len, code,
+                          self.state)
+        return RecvPieces(frames, Batch(msg, msg_off, msg_len), event, status)
+
+
 @dataclass
 class Controls:
     wire: Batch            # one frame per entry at 144 * i; len 0 = refused

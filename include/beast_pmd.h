@@ -365,7 +365,8 @@ enum bpmd_ws_error {
  * One deliberate difference from Beast: only whole frames are consumed.  A
  * frame whose header or payload the buffer cuts stays unconsumed, where
  * Beast hands over the part of a data frame's payload that has arrived
- * (rd_remain, read.hpp:1201-1280).  So that a frame which can never fit is
+ * (rd_remain, read.hpp:1201-1280); bpmd_receive_pieces_batch (below) is the
+ * call that does.  So that a frame which can never fit is
  * refused at once, not waited for, a data frame whose rd_size + length
  * exceeds d_out_cap[i] is refused at header time with buffer_overflow, after
  * parse_fh's own checks.
@@ -429,7 +430,7 @@ int bpmd_unframe_batch(int role, int pmd_on, uint64_t msg_max, const uint8_t* d_
  * it.  Deliberately out of scope: context-takeover receives
  * (bpmd_receive_takeover_batch, below, is this call over connection buffers),
  * more than one event per entry and call, and partial frames
- * (bpmd_unframe_batch, above).
+ * (bpmd_unframe_batch, above; bpmd_receive_pieces_batch, below, takes them).
  * n == 0 is a no-op; BPMD_R_INVALID_ARGUMENT for a role that is neither
  * value, a NULL required pointer, BPMD_F_RAW or (pmd_on) a NULL cfg;
  * BPMD_R_DOMAIN_ERROR for window bits outside 8..15; BPMD_R_NO_DEVICE
@@ -692,7 +693,8 @@ int bpmd_slide_batch(uint8_t* d_buf, const uint64_t* d_base, const uint32_t* d_p
  *
  * Everything is enqueued on `stream` and no step reads anything back: which
  * connections slide is decided on the device.  Out of scope as for
- * bpmd_receive_batch: more than one event per entry and call, partial frames.
+ * bpmd_receive_batch: more than one event per entry and call, partial frames
+ * (bpmd_receive_pieces_batch, below, takes them).
  * n == 0 is a no-op; BPMD_R_INVALID_ARGUMENT for a role that is neither
  * value, a NULL pointer other than d_state, BPMD_F_RAW, a NULL cfg or
  * slot_bytes <= 2 * W; BPMD_R_DOMAIN_ERROR for window bits outside 8..15;
@@ -880,6 +882,107 @@ int bpmd_send_pieces_batch(const bpmd_cfg* cfg, const uint8_t* d_in, const uint6
                            const uint32_t* d_key_base, uint8_t* d_wire, uint64_t wire_cap, uint64_t* d_wire_off,
                            uint32_t* d_wire_len, uint8_t* d_compressed, int32_t* d_status, uint64_t* d_total,
                            void* d_work, void* stream);
+
+/* Receive messages in pieces: read_some as Beast runs it (read.hpp:1063-1385),
+ * one piece per connection per call.  bpmd_send_pieces_batch's counterpart,
+ * and bpmd_receive_batch / bpmd_receive_takeover_batch for peers whose frames
+ * or messages are larger than the buffers a connection should hold: a data
+ * frame is taken as far as its bytes have arrived, unmasked with the key as
+ * rotated so far, inflated by the per-stream state machine that keeps its
+ * window and its half-decoded symbol on the device, checked as UTF-8 with the
+ * cut code point carried, and delivered.  Entry i is connection i, once per
+ * call.  pmd_on == 0: cfg, d_zstate, d_msg, d_msg_off, d_msg_cap and d_work
+ * may be NULL.
+ *
+ * State.  d_state[i] (required) is read_some's state between calls, all zero
+ * between messages.  d_zstate holds n consecutive inflater states of
+ * bpmd_receive_pieces_zstate_bytes() bytes each (a multiple of 16; d_zstate
+ * 16-byte aligned) that the caller zeroes once: all zero is a new connection,
+ * whose window bits the call sets from cfg->window_bits on first use.  The
+ * state keeps its window, so context takeover needs nothing, and a
+ * no_context_takeover connection uses the same call with the same state
+ * (Beast's zi.clear() is a no-op, impl_base.hpp:193-202).
+ *
+ * Frame walk.  bpmd_unframe_batch's walk with the same header checks, events
+ * and control slots, except:
+ *   - the bytes gathered in this call start at offset 0 of the out slot
+ *     d_out + d_out_off[i], which is reused from call to call; d_out_len[i] is
+ *     the piece's gathered length.  At most d_out_cap[i] - 4 payload bytes are
+ *     gathered per call; an entry with d_out_cap[i] < 8 gathers nothing and
+ *     gets BPMD_WS_BUFFER_OVERFLOW.  No frame is refused for its size.
+ *   - a data frame whose payload the buffer or the slot cuts is consumed as
+ *     far as it goes: its header and the bytes taken count in d_consumed[i],
+ *     and rd_remain, the rotated rd_key and rd_fin carry the rest; a call that
+ *     starts with rd_remain > 0 takes payload bytes first.  Control frames and
+ *     cut headers stay whole and unconsumed (stream_impl.hpp:817-823).
+ *   - the walk also stops when the slot is full: BPMD_EV_NEED_MORE with status
+ *     0, and the caller calls again with the unconsumed rest.
+ * BPMD_EV_MESSAGE means the FIN frame's last payload byte was taken: this
+ * piece is its message's last.  A control frame between fragments stops the
+ * walk and the data gathered before it is still this call's piece, as are the
+ * bytes gathered before a refused header.  d_op / d_compressed describe the
+ * message the piece belongs to.
+ *
+ * Piece.
+ *   - d_compressed[i] == 0: the piece stays in the out slot, d_msg_len[i] =
+ *     d_out_len[i]; msg_max is applied at header time.
+ *   - d_compressed[i] != 0: behind a message's last piece the walk appends
+ *     00 00 FF FF in the slot, and one inflate_stream::write(Flush::sync) runs
+ *     over piece (+ tail) from connection i's state into d_msg + d_msg_off[i]
+ *     with the room eff = min(d_msg_cap[i], msg_max - rd_size + 1) (all of
+ *     d_msg_cap[i] when msg_max == 0).  An empty last piece still inflates the
+ *     tail; an empty piece inside a message runs nothing.  d_msg_len[i] = the
+ *     bytes produced (0 after a zlib::error, which hands nothing over, as in
+ *     Beast).  d_status[i], in stream order: the zlib::error other
+ *     than need_buffers; else BPMD_WS_MESSAGE_TOO_BIG when rd_size + produced
+ *     > msg_max; else BPMD_WS_BUFFER_OVERFLOW when input was left, i.e. the
+ *     room ran out: the connection is dropped.  A piece inside a message that
+ *     consumes its input with output still pending in the decoder is no
+ *     error: the rest comes with the next piece.
+ *   - text (d_op[i] == 1), status 0 so far: utf8_b[0..utf8_n) followed by the
+ *     piece are checked where the piece lies: BPMD_BAD_FRAME_PAYLOAD when they
+ *     are no prefix of well-formed UTF-8, or when the message ends inside a
+ *     code point; else the bytes of a cut code point are the new carry.
+ *   - a frame error reported behind a piece that was fine stays in d_status[i].
+ * At a message's end the state is all zero again.  Any error leaves the
+ * connection to be dropped; its states are unspecified from then on.
+ *
+ * No byte of d_out outside [d_out_off[i], d_out_off[i] + d_out_cap[i]) is
+ * written, none of d_msg outside [d_msg_off[i], d_msg_off[i] + eff) and none
+ * of an entry that ran no inflater; d_zstate only inside connection i's state;
+ * d_wire is not modified.  The inflater loads its input 16 bytes at a time
+ * from the slot's start: the memory behind d_out must be readable for 15 bytes
+ * past every slot.  An entry with d_wire_len[i] == 0 changes no state and no
+ * slot.  d_work: bpmd_receive_pieces_work_bytes(n) (host only) bytes, per
+ * entry the inflater's call record and its result; one workspace serves one
+ * call at a time.  Everything is enqueued on `stream` and nothing is read
+ * back.
+ *
+ * n == 0 is a no-op; BPMD_R_INVALID_ARGUMENT for a role that is neither value,
+ * a NULL required pointer, BPMD_F_RAW or (pmd_on) a NULL cfg;
+ * BPMD_R_DOMAIN_ERROR for window bits outside 8..15; BPMD_R_NO_DEVICE without a
+ * GPU.  Out of scope: more than one message per entry and call, and resuming a
+ * piece whose output room ran out with input left. */
+typedef struct bpmd_rd_piece_state {
+    uint64_t rd_size;     /* Beast's rd_size: bytes of the current message delivered so far
+                             (gathered bytes of a plain message, inflated bytes of a compressed one) */
+    uint64_t rd_remain;   /* payload bytes of the current data frame that have not arrived yet */
+    uint32_t rd_key;      /* that frame's key, rotated so that byte 0 applies to its next payload byte (mask.ipp:29-36) */
+    uint8_t  rd_cont, rd_op, rd_deflated;
+    uint8_t  rd_fin;      /* FIN of the frame rd_remain belongs to */
+    uint8_t  utf8_n;      /* 0..3: bytes of a code point the text delivered so far ends inside */
+    uint8_t  utf8_b[3];
+    uint8_t  reserved[4]; /* zero */
+} bpmd_rd_piece_state;    /* 32 bytes; all zero = between messages */
+size_t bpmd_receive_pieces_zstate_bytes(void);
+size_t bpmd_receive_pieces_work_bytes(uint32_t n);
+int bpmd_receive_pieces_batch(const bpmd_cfg* cfg, int role, int pmd_on, uint64_t msg_max, const uint8_t* d_wire,
+                              const uint64_t* d_wire_off, const uint32_t* d_wire_len, uint32_t n,
+                              bpmd_rd_piece_state* d_state, void* d_zstate, uint8_t* d_out, const uint64_t* d_out_off,
+                              const uint32_t* d_out_cap, uint32_t* d_out_len, uint8_t* d_op, uint8_t* d_compressed,
+                              uint8_t* d_event, int32_t* d_status, uint32_t* d_consumed, uint8_t* d_ctl,
+                              uint8_t* d_ctl_len, uint16_t* d_close_code, uint8_t* d_msg, const uint64_t* d_msg_off,
+                              const uint32_t* d_msg_cap, uint32_t* d_msg_len, void* d_work, void* stream);
 
 /* ---------------------------------------------------------------------
  * Per-stream API behind the C++ compatibility facade
