@@ -142,18 +142,31 @@ def main():
             ok = False
             print("failed checks in call", k, file=sys.stderr)
     if piece:
+        # a message takes ceil(longest wire / piece) calls, a connection with a shorter wire fewer: each is judged
+        # at its own last non-empty piece, where its message must end; an empty piece behind it takes and
+        # delivers nothing and asks for more
         reset_p()
         for k in range(cycle):
             got = [b""] * len(sample)
-            for data, off, ln in split[k]:
+            last = (wires[k].len.to(torch.int64) + piece - 1) // piece - 1
+            for j, (data, off, ln) in enumerate(split[k]):
                 pieces_call(data, off, ln)
                 torch.cuda.synchronize()
-                ok = ok and not po["status"].any() and torch.equal(po["consumed"], ln)
+                ends, empty = last == j, ln == 0
+                checks = {"status": not po["status"].any(), "consumed": torch.equal(po["consumed"], ln),
+                          "message at the last piece": bool((po["event"][ends] == pmd.EV_MESSAGE).all()),
+                          "need_more elsewhere": bool((po["event"][~ends] == pmd.EV_NEED_MORE).all()),
+                          "nothing from an empty piece": not po["msg_len"][empty].any() and not po["out_len"][empty].any()}
+                for name, good in checks.items():
+                    if not good:
+                        ok = False
+                        print("failed check in message", k, "piece", j, ":", name, file=sys.stderr)
                 ml = po["msg_len"].cpu().tolist()
                 for a, c in enumerate(sample):
                     got[a] += bytes(p_msg[c * size:c * size + ml[c]].cpu().numpy())
-            ok = ok and all(got[a] == texts[k][deal[c]] for a, c in enumerate(sample))
-            ok = ok and bool((po["event"] == pmd.EV_MESSAGE).all())
+            if not all(got[a] == texts[k][deal[c]] for a, c in enumerate(sample)):
+                ok = False
+                print("failed check in message", k, ": reassembled bytes", file=sys.stderr)
 
     new = "split" if piece else "pieces"     # with --piece the slot is piece + 4 bytes: no whole message fits a call
     meds = {k: [] for k in ("takeover_events", "takeover_host", new + "_events", new + "_host")}

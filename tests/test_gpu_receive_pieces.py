@@ -8,7 +8,13 @@ The gathered slots, the message slots and the inflater states stay on the
 device from call to call; the slots are filled with a canary and carry guard
 bytes.  After every call every output array, the whole d_state, the whole
 d_out, d_msg (d_msg_len bytes compared, the rest of the inflater's room free,
-everything else unchanged), the control slots and all guards equal the model."""
+everything else unchanged), the control slots and all guards equal the model.
+
+The toy-sized cases are built here; the long ones (16 KiB messages in read
+buffer pieces, a window that wraps many times, one piece over the inflater's
+staging and ring, UTF-8 across the scan's 1 KiB rounds) come from
+tests/receive_pieces_cases.py, which the CPU suite runs through the model
+alone (tests/test_receive_pieces_cases.py)."""
 import ctypes
 import random
 
@@ -17,14 +23,15 @@ import pytest
 
 from oracle import oracle as O
 from tests import frame_parse_model as FM
+from tests import receive_pieces_cases as C
 from tests import receive_pieces_model as M
 from tests import takeover_cases as TC
+from tests.receive_pieces_cases import drive, events
 
 pytestmark = pytest.mark.gpu
 
 CANARY, GUARD = 0xA5, 64
 SERVER, CLIENT = FM.SERVER, FM.CLIENT
-EV = {FM.EV_PING: "ping", FM.EV_PONG: "pong", FM.EV_CLOSE: "close"}
 
 
 def _pmd():
@@ -46,7 +53,8 @@ def _layout(caps, residues):
 class Rig:
     """n connections' device state and the model's record of it"""
 
-    def __init__(self, n, role, wbits=15, pmd_on=True, msg_max=0, out_cap=64, msg_cap=4096, out_res=None, wire_res=None):
+    def __init__(self, n, role, wbits=15, pmd_on=True, msg_max=0, out_cap=64, msg_cap=4096, out_res=None, wire_res=None,
+                 msg_res=None):
         torch, pmd = _pmd()
         self.n, self.role, self.pmd_on, self.msg_max = n, role, pmd_on, msg_max
         self.L = pmd._recv_pc_lib()
@@ -56,7 +64,7 @@ class Rig:
         self.out_cap, self.msg_cap = lst(out_cap), lst(msg_cap)
         self.wire_res = lst(wire_res or 0)
         self.h_out_off, out_bytes = _layout(self.out_cap, lst(out_res or 0))
-        self.h_msg_off, msg_bytes = _layout(self.msg_cap, [0] * n)
+        self.h_msg_off, msg_bytes = _layout(self.msg_cap, lst(msg_res or 0))
         self.h_out = np.full(out_bytes, CANARY, dtype=np.uint8)
         self.h_msg = np.full(msg_bytes, CANARY, dtype=np.uint8)
         self.d_out = torch.from_numpy(self.h_out.copy()).to(dev)
@@ -144,44 +152,6 @@ class Rig:
             assert np.array_equal(g_msg, self.h_msg), (self.calls, np.flatnonzero(g_msg != self.h_msg)[:8])
             assert bool((self.d_z[n * self.zb:] == CANARY).all())
         return ps
-
-
-def drive(rig, wires, steps, msg_cap=None):
-    """Connection i gets steps[i] more bytes of wires[i] per call until it has
-    taken them all or failed.  Returns per connection its pieces."""
-    n = rig.n
-    steps = [steps] * n if isinstance(steps, int) else steps
-    fed, used, done, log = [0] * n, [0] * n, [False] * n, [[] for _ in range(n)]
-    while not all(done):
-        chunk = []
-        for i in range(n):
-            if not done[i]:
-                fed[i] = min(len(wires[i]), fed[i] + steps[i])
-            chunk.append(b"" if done[i] else wires[i][used[i]:fed[i]])
-        for i, p in enumerate(rig.call(chunk, msg_cap)):
-            if done[i]:
-                continue
-            used[i] += p.stop.consumed
-            log[i].append(p)
-            stuck = fed[i] == len(wires[i]) and p.stop.consumed == 0 and p.stop.event == FM.EV_NEED_MORE
-            done[i] = bool(p.status) or used[i] == len(wires[i]) or stuck
-    return log
-
-
-def events(pieces):
-    """what a connection's pieces amount to: [("message", op, compressed, bytes) | ("ping", payload) | ("error", status)]"""
-    out, cur = [], b""
-    for p in pieces:
-        cur += p.delivered
-        if p.status:
-            out.append(("error", p.status))
-            break
-        if p.stop.event == FM.EV_MESSAGE:
-            out.append(("message", p.stop.op, p.stop.compressed, cur))
-            cur = b""
-        elif p.stop.event != FM.EV_NEED_MORE:
-            out.append((EV[p.stop.event], p.stop.ctl))
-    return out
 
 
 def keyed(role, rng):
@@ -546,3 +516,59 @@ def test_round_trip_from_the_piece_sender(sender_role):
                 got[c].append((cur[c], ops[c]))
                 cur[c] = b""
     assert got == want
+
+
+# ---- long messages, pieces over the kernels' thresholds (inputs: tests/receive_pieces_cases.py, whose conditions
+# tests/test_receive_pieces_cases.py checks on the CPU)
+
+def run_case(case):
+    """the case on a Rig of its own: every call compared with the model, then
+    what each connection's pieces amount to"""
+    rig = Rig(case.n, case.role, **case.rig)
+    log = case.run(rig)
+    for c in range(case.n):
+        assert events(log[c]) == case.want[c], (c, case.tags[c])
+        bad = None if case.fail_piece is None else case.fail_piece[c]
+        assert [p.status for p in log[c]] == ([0] * len(log[c]) if bad is None else [0] * bad + [M.BAD_FRAME_PAYLOAD]), c
+    return rig, log
+
+
+def test_long_messages_in_read_buffer_pieces():
+    """70 kept-context connections, four 16 KiB messages each of json, binary,
+    random, corpus1 or zeros, through a 1 536-byte read buffer into 1 540-byte
+    out slots; out slots, wire and message slots at every residue mod 16.  The
+    pieces take the copy's and the scan's second round, every connection
+    inflates 64 KiB through its 32 KiB window in calls that load the saved
+    window and write it back, random's stored blocks span pieces, and a zeros
+    piece delivers FLUSH_AT bytes from a few"""
+    rig, log = run_case(C.long_messages())
+    assert rig.calls >= 4 * 16384 // 1536 and max(p.out_len for ps in log for p in ps) == 1536
+
+
+@pytest.mark.parametrize("wbits", [9, 10])
+def test_small_window_wraps_many_times(wbits):
+    """the same with 3 000-byte json messages in 100-byte pieces at window
+    bits 9 and 10: the saved window wraps between calls about twenty times"""
+    run_case(C.small_window(wbits))
+
+
+def test_one_piece_over_staging_and_ring():
+    """one call per message: 70 000 stored bytes (input far over the 4 KiB
+    staging, from a misaligned slot; output that wraps the 64 KiB ring) or
+    100 000 zeros from under 200 wire bytes, then a json message and an echo
+    whose matches reach 32 000 bytes back into the window that call left"""
+    rig, log = run_case(C.over_staging_ring())
+    assert rig.calls == 3 and {len(ps[0].delivered) for ps in log} == {70000, 100000}
+
+
+@pytest.mark.parametrize("comp", [0, 1])
+def test_utf8_over_scan_rounds(comp):
+    """2 600-byte text pieces in the out slot (comp 0) or the message slot
+    (comp 1) at every residue: 2-, 3- and 4-byte code points at every split
+    across the boundaries between the scan's rounds of 1 024 bytes, where lane
+    63 fetches its own look-ahead; the same texts cut inside such a code point,
+    so that a piece over 1 KiB leaves a carry or meets one; and continuation
+    bytes replaced, lone continuations, E0 80 80, ED A0 80 and F4 90 80 80
+    across the same boundaries, each failing in the piece the model says"""
+    rig, log = run_case(C.utf8_rounds(comp))
+    assert rig.calls == 2
